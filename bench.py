@@ -1,6 +1,6 @@
 """bench.py -- scenes/s of the CN-RMA hot path (dense unprojection -> RMA -> voxelise -> FCAF3D -> decode), forward.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NS|S|St|tiny]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NS|S|St|tiny] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
            bench.py --gpus N --steps K --warmup W
 
@@ -11,12 +11,18 @@ measured in the same run and printed as the labelled block "S" of the same JSON 
 A *scene* goes through the whole path as ONE replayed HIP graph (pipeline.StaticScene: ~350 launches, no device->host
 read); inputs (feature maps as the 2D backbone writes them, NCHW fp32, and the TSDF) are resident in HBM; `--slots`
 graphs on their own streams are in flight so that the latency-bound small kernels of one scene overlap the large kernels
-of another.  A *step* = one wave of `scenes_per_step` scenes per GPU (chosen from the warm-up so that the K timed steps
-take >= --window-s seconds; printed in `config`).  >= 8 DISTINCT scenes (own feature tensors, own furniture in the TSDF)
-are rotated.  The K steps are timed three times (each window bracketed by barrier + synchronize, MAX over ranks); `value`
-is the median window.  Scenes are independent: N GPUs process N x scenes_per_step scenes per step (weak scaling), the
-only exchange is ONE all-gather of the padded detections per step over RCCL.
-Rank 0 prints ONE JSON line carrying `roofline` and `cpu_baseline`.
+of another.  A *step* = one wave of `scenes_per_step` scenes per GPU (default: one pass over the rotated scenes, rounded
+up to whole rounds over the slots; printed in `config`).  >= 8 DISTINCT scenes (own feature tensors, own furniture in the
+TSDF) are rotated.  After W warm-up steps exactly K steps are timed in one window (bracketed by barrier + synchronize, MAX
+over ranks; --windows R times R windows of K steps, `value` is then the median window).  Scenes are independent: N GPUs
+process N x scenes_per_step scenes per step (weak scaling), the only exchange is ONE all-gather of the padded detections
+per step over RCCL.  Rank 0 prints ONE JSON line.
+
+A plain run measures the headline workload only.  --full adds what takes runs of its own: the per-kernel profile and
+roofline, the secondary blocks (S shape, exact-fp32 convolutions, NCHW hand-off, through the plugin, ScanNet test shape,
+ARKit config, training step) and the CPU baselines, and writes bench_detail.json.  --dump-outputs DIR writes what the
+timed path handed its caller in the last timed step as .npy files (dump_outputs()); the inputs are a function of the
+arguments, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -155,9 +161,15 @@ def parse():
     ap.add_argument("--scenes-per-pass", type=int, default=0,
                     help="scenes collated into one sparse-network pass per graph (pipeline.StaticBatch; 1 = one scene per graph, "
                          "0 = the workload's default)")
-    ap.add_argument("--scenes-per-step", type=int, default=0, help="0 = chosen from the warm-up (see --window-s)")
-    ap.add_argument("--window-s", type=float, default=2.0, help="minimum length of one timed window of K steps")
-    ap.add_argument("--windows", type=int, default=3)
+    ap.add_argument("--scenes-per-step", type=int, default=0, help="0 = one pass over the rotated scenes, rounded up to whole "
+                    "rounds over the slots (or chosen from the warm-up with --window-s)")
+    ap.add_argument("--window-s", type=float, default=0.0, help="> 0 and no --scenes-per-step: scenes per step chosen from the "
+                    "warm-up so that one timed window of K steps takes >= this many seconds")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of K steps each (value = the median window)")
+    ap.add_argument("--full", action="store_true", help="also the per-kernel profile / roofline, the secondary blocks and the "
+                    "CPU baselines (--no-profile, --no-secondary, --no-cpu-baseline leave parts out), and bench_detail.json")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="after the timed steps, write the detections the timed path "
+                    "returned in its last step as DIR/<name>.npy (see dump_outputs())")
     ap.add_argument("--eager", action="store_true", help="no graphs: the eager path (device->host reads per scene)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
@@ -175,7 +187,8 @@ def parse():
                          "hands over (MultiViewBase.channels_last_2d: the 2D network runs in torch.channels_last), read in place; "
                          "nchw = the reference's layout, converted by the layout pass inside the timed path")
     ap.add_argument("--detail", default="", help="where the full result (kernel tables, per-layer convolution table, stage times, notes) "
-                    "goes; default: bench_detail.json beside bench.py (and a copy under gpurun_out/ when that directory exists)")
+                    "goes; default with --full: bench_detail.json beside bench.py (and a copy in the run's output directory when "
+                    "there is one); a plain run writes it only to the path given here")
     ap.add_argument("--dump-exchange", default="", help="test aid: directory that receives, after the last timed step of the main "
                     "workload, every rank's own padded detections (rank<r>_of<N>.npz) and rank 0's gathered block (gathered.npz)")
     ap.add_argument("--as-rank", type=int, default=-1, help="test aid (single process): generate the scenes rank R of a multi-rank "
@@ -428,7 +441,8 @@ class Workload:
         self.cfg = pipeline.SceneConfig(self.dims, stride=self.stride, max_points=500000, sampler="device")
         self.det_w = (6 if n_reg == 6 else 7) + n_classes
         self.slots = []
-        self._k = 0
+        self._k = 0                                        # scenes run so far (the rotation index)
+        self.steps_run = 0
 
     def _build_plugin_model(self, n_classes, n_reg):
         """the registered detector built from the ScanNet config's model section (hot-path form: feature maps and TSDF
@@ -519,17 +533,23 @@ class Workload:
     def step(self):
         """one wave of sps scenes on this GPU (+ one all-gather of the detections when there are several ranks)"""
         torch = self.torch
+        self.steps_run += 1
         if self.plugin:
+            self.last_names = []                                # the scenes of this step (their result files: dump_outputs)
             with torch.no_grad():
                 for j in range(self.sps):
-                    self._plugin_scene(self.scenes[self._k % len(self.scenes)])
+                    s = self.scenes[self._k % len(self.scenes)]
+                    self._plugin_scene(s)
+                    self.last_names.append(s["name"])
                     self._k += 1
             return
         if self.args.eager:
+            self.last_step = []                                 # (bboxes, scores) of every scene of this step (dump_outputs)
             for j in range(self.sps):
                 s = self.scenes[self._k % len(self.scenes)]
                 self._k += 1
                 self.last = self.pipeline.forward_scene(self.cfg, self.backbone, self.head, s["features"], s["projection"], s["tsdf"])
+                self.last_step.append((self.last["bboxes"], self.last["scores"]))
             return
         main = torch.cuda.current_stream()
         if getattr(self, "B", 1) > 1:
@@ -544,7 +564,7 @@ class Workload:
                 sb = self.slots[i]
                 out = sb.run(group)
                 with torch.cuda.stream(sb.stream):
-                    nb = out["bboxes"].shape[2]
+                    nb = self.box_w = out["bboxes"].shape[2]
                     self.det[j:j + B, :, :nb].copy_(out["bboxes"], non_blocking=True)
                     self.det[j:j + B, :, nb:].copy_(out["scores"], non_blocking=True)
                     self.det_valid[j:j + B].copy_(out["valid"], non_blocking=True)
@@ -559,7 +579,7 @@ class Workload:
                 st.done.synchronize()                           # host paces itself: a slot is refilled when its scene has left it
             out = st.run(s["features"], s["projection"], s["tsdf"])
             with torch.cuda.stream(st.stream):                  # results leave the slot's static buffers in stream order
-                nb = out["bboxes"].shape[1]
+                nb = self.box_w = out["bboxes"].shape[1]
                 self.det[j, :, :nb].copy_(out["bboxes"], non_blocking=True)
                 self.det[j, :, nb:].copy_(out["scores"], non_blocking=True)
                 self.det_valid[j].copy_(out["valid"], non_blocking=True)
@@ -610,10 +630,13 @@ class Workload:
 
 
 def time_windows(wl, args, world, barrier):
-    """warm-up, choice of scenes_per_step, then `windows` windows of exactly `steps` steps; returns per-window seconds"""
+    """warm-up, then `windows` windows of exactly `steps` steps; returns (scenes per step, per-window seconds).  The step
+    size is fixed by the arguments -- one pass over the rotated scenes, rounded up to whole rounds over the slots -- so that
+    the same arguments run the same scenes in the same order; only --window-s > 0 chooses it from the warm-up."""
     import torch
     q = max(1, len(wl.slots)) * getattr(wl, "B", 1)                     # scenes of one round over the slots
-    sps = args.scenes_per_step or max(2, q)
+    adaptive = not args.scenes_per_step and args.window_s > 0
+    sps = args.scenes_per_step or (max(2, q) if adaptive else -(-len(wl.scenes) // q) * q)
     sps = -(-sps // getattr(wl, "B", 1)) * getattr(wl, "B", 1)
     wl.alloc_step_buffers(sps)
     barrier()
@@ -623,7 +646,7 @@ def time_windows(wl, args, world, barrier):
     wl.drain()
     barrier()
     warm = (time.perf_counter() - t0) / max(1, args.warmup) / sps        # seconds per scene, warm-up estimate
-    if not args.scenes_per_step:
+    if adaptive:
         want = args.window_s / max(1, args.steps) / max(warm, 1e-6)
         sps = int(min(256, max(q, -(-int(want + 0.999) // q) * q)))
         if world > 1:
@@ -636,6 +659,7 @@ def time_windows(wl, args, world, barrier):
             wl.step()
     barrier()
     secs, per_rank = [], []
+    before = wl.steps_run
     for _ in range(max(1, args.windows)):
         barrier()
         t0 = time.perf_counter()
@@ -653,11 +677,63 @@ def time_windows(wl, args, world, barrier):
             dt = max(per_rank[-1])                                       # MAX over ranks
         secs.append(dt)
     wl.per_rank_window_s = per_rank
+    wl.timed_steps = wl.steps_run - before
     return sps, secs
 
 
-def measure(name, device, rank, world, args, barrier, precision=None, plugin=False, layout=None, config=None):
-    """build + time one workload; returns the result block"""
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: what the timed path handed its caller in the LAST timed step, scene by scene in step order -- the
+    live detection rows (padding rows dropped), concatenated over the scenes and their levels:
+        bboxes.npy  [R, 6 | 7] float32     scores.npy  [R, n_classes] float32
+        rows.npy    [scenes, levels] float64, live rows per scene and level (one column on the eager and the plugin path)
+    Graph path: the step buffers hold every scene's padded block in the layout of the slot's outputs, and the slot's own
+    detections() picks the live rows out of them (refused when a step violated the static plan).  Plugin path: one entry
+    per distinct scene of the step, read from its result file -- a scene the step met twice left only its later result.
+    Scenes past DUMP_LIMIT_BYTES in all are left out (the first scenes of the step are kept)."""
+    import numpy as np
+    torch = wl.torch
+    torch.cuda.synchronize()
+    scenes = []                                                          # per scene: (bboxes, scores, live rows per level)
+    if wl.plugin:
+        for name in dict.fromkeys(wl.last_names):                        # a scene's file holds its latest result
+            z = np.load(os.path.join(wl.save_dir, name, name + "_bbox_raw.npz"))
+            scenes.append((z["bboxes"], z["scores"], [len(z["bboxes"])]))
+    elif wl.args.eager:
+        for b, sc in wl.last_step:
+            scenes.append((b.cpu().numpy(), sc.cpu().numpy(), [b.shape[0]]))
+    else:
+        bad = wl.violations()
+        if bad:
+            raise RuntimeError(f"{bad} static-plan violation(s) in the timed steps: the step buffers hold no valid detections")
+        B, slot = getattr(wl, "B", 1), wl.slots[0]
+        out = {k: v for k, v in slot.out.items() if k != "done"}
+        out["status"] = torch.zeros_like(slot.out["status"])              # checked above, over every step
+        valid = wl.det_valid.cpu().numpy()
+        for j in range(0, wl.sps, B):
+            blk = slice(j, j + B) if B > 1 else j
+            out.update(bboxes=wl.det[blk, ..., :wl.box_w], scores=wl.det[blk, ..., wl.box_w:], valid=wl.det_valid[blk])
+            res = slot.detections(out)
+            for b, (bx, sc, _) in enumerate(res if B > 1 else [res]):
+                scenes.append((bx.cpu().numpy(), sc.cpu().numpy(), list(valid[j + b])))
+    kept, total = [], 0
+    for b, sc, r in scenes:
+        n = b.nbytes + sc.nbytes + 8 * len(r)
+        if kept and total + n > DUMP_LIMIT_BYTES:
+            break
+        kept.append((b, sc, r))
+        total += n
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "bboxes.npy"), np.concatenate([b for b, _, _ in kept]).astype(np.float32))
+    np.save(os.path.join(out_dir, "scores.npy"), np.concatenate([sc for _, sc, _ in kept]).astype(np.float32))
+    np.save(os.path.join(out_dir, "rows.npy"), np.asarray([r for _, _, r in kept], dtype=np.float64))
+    log(f"outputs of the last step: {len(kept)} of {len(scenes)} scenes, {total / 2 ** 20:.1f} MiB -> {out_dir}")
+
+
+def measure(name, device, rank, world, args, barrier, precision=None, plugin=False, layout=None, config=None, dump=""):
+    """build + time one workload; returns the result block.  dump: directory for dump_outputs() (rank 0)"""
     import torch
     from cnrma_amd import sparse as S
     prev = S.CONV_PRECISION
@@ -672,6 +748,8 @@ def measure(name, device, rank, world, args, barrier, precision=None, plugin=Fal
         c0 = os.times()
         sps, secs = time_windows(wl, args, world, barrier)
         c1 = os.times()
+        if dump and rank == 0:
+            dump_outputs(wl, dump)
         if getattr(args, "dump_exchange", "") and not plugin and precision is None and layout is None and getattr(wl, "det", None) is not None:
             import numpy as np
             torch.cuda.synchronize()
@@ -686,7 +764,8 @@ def measure(name, device, rank, world, args, barrier, precision=None, plugin=Fal
         block = dict(value=world * args.steps * sps / med, ms_per_step=med / args.steps * 1e3, ms_per_scene=med / args.steps / sps * 1e3,
                      scenes_per_step=sps, windows_scenes_per_s=[world * args.steps * sps / s for s in secs],
                      window_s=med, plan_violations=bad, distinct_scenes=len(wl.scenes), input_GB=wl.input_bytes / 1e9,
-                     host_cpu_cores_busy=round(((c1.user - c0.user) + (c1.system - c0.system)) / max(sum(secs), 1e-9), 2))
+                     host_cpu_cores_busy=round(((c1.user - c0.user) + (c1.system - c0.system)) / max(sum(secs), 1e-9), 2),
+                     timed_steps=wl.timed_steps, steps_run=wl.steps_run, scenes_run=wl._k)
         block.update(wl.sizes())
         if world > 1:
             block["per_rank_window_s"] = wl.per_rank_window_s            # [window][rank]: what every rank's clock saw
@@ -912,7 +991,7 @@ def compact_line(result):
     if result.get("dist"):
         d = result["dist"]
         line["dist"] = dict(world_size=d.get("world_size"), backend=d.get("backend"))
-    line["detail"] = DETAIL_NAME
+    line["detail"] = result.get("detail", DETAIL_NAME)                 # None: a plain run wrote no detail file
     line = _r(line)
     text = json.dumps(line, allow_nan=False, separators=(",", ":"))
     if len(text) >= LINE_LIMIT:                                          # never print a line the driver cannot parse
@@ -925,11 +1004,14 @@ def compact_line(result):
     return text
 
 
-def emit(result, detail_path=""):
-    """detail file + stderr first, then the ONE stdout line, last thing this process prints"""
+def emit(result, detail_path="", default_detail=True):
+    """detail file + stderr first, then the ONE stdout line, last thing this process prints.  No detail_path and not
+    default_detail (a plain run): no detail file"""
     text = compact_line(result)
     detail = json.dumps(result, indent=1, default=str)
     targets = [detail_path] if detail_path else [os.path.join(ROOT, DETAIL_NAME), os.path.join(ROOT, "gpurun_out", DETAIL_NAME)]
+    if not detail_path and not default_detail:
+        targets = []
     for path in targets:
         try:
             if os.path.isdir(os.path.dirname(os.path.abspath(path))):
@@ -937,7 +1019,7 @@ def emit(result, detail_path=""):
                     f.write(detail)
         except OSError as e:                                             # a read-only tree must not cost the line
             log(f"could not write {path}: {e}")
-    log(f"detail: {DETAIL_NAME} ({len(detail)} bytes); line: {len(text)} bytes")
+    log(f"detail: {(detail_path or DETAIL_NAME) if targets else 'not written'} ({len(detail)} bytes); line: {len(text)} bytes")
     sys.stderr.flush()
     sys.stdout.write(text + "\n")
     sys.stdout.flush()
@@ -986,7 +1068,11 @@ def main():
         from cnrma_amd import rma
         rma.dense_tuning(**{k: int(v) for k, v in (kv.split("=") for kv in args.dense_tuning.split(","))})
 
-    wl, main_block = measure(args.workload, device, rank, world, args, barrier, plugin=args.through_plugin)
+    wl, main_block = measure(args.workload, device, rank, world, args, barrier, plugin=args.through_plugin, dump=args.dump_outputs)
+    # what takes runs of its own: only with --full
+    profile = args.full and not args.no_profile
+    secondary = args.full and not args.no_secondary
+    cpu = args.full and not args.no_cpu_baseline
     V, C, H, W, dims, stride = wl.V, wl.C, wl.H, wl.W, wl.dims, wl.stride
     result = {
         "metric": "scenes/sec fwd (40-view->192^3 voxel): dense unprojection + RMA + voxelise + FCAF3D + decode",
@@ -1014,7 +1100,7 @@ def main():
                    "host_cores": os.cpu_count()},
     }
     for k in ("scenes_per_step", "ms_per_scene", "windows_scenes_per_s", "window_s", "plan_violations", "host_cpu_cores_busy",
-              "graph_nodes_per_scene"):
+              "graph_nodes_per_scene", "timed_steps", "steps_run", "scenes_run"):
         result[k] = main_block[k]
     result["feature_layout"] = wl.layout
     if world > 1:
@@ -1025,7 +1111,7 @@ def main():
     for k in ("M_rows", "M_selected", "M_unique", "level_rows", "head_rows"):
         result["config"][k] = main_block[k]
 
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and profile:
         log("per-kernel profile (eager pass)")
         result["roofline"] = profile_block(wl, main_block, args.workload)
         for k in ("kernels", "stage_ms", "conv", "conv_layers", "algorithmic_GB_per_scene", "whole_path_hbm", "pmc_sq"):
@@ -1038,7 +1124,7 @@ def main():
     if args.through_plugin:
         result["config"]["driver"] = ("registered RayMarching detector: model(return_loss=False, **data) per scene, "
                                       "{scene}_bbox_raw.npz written per scene (tmpfs), flush inside the timed window")
-    if not args.no_secondary and not args.through_plugin:
+    if secondary and not args.through_plugin:
         # ---- the same workload driven through the plugin API (test.py:205-214 -> RayMarching.forward_test)
         wlp, bp = measure(args.workload, device, rank, world, args, barrier, plugin=True)
         result["through_plugin"] = {k: bp[k] for k in ("value", "ms_per_step", "ms_per_scene", "scenes_per_step",
@@ -1054,7 +1140,7 @@ def main():
         shutil.rmtree(wlp.save_dir, ignore_errors=True)
         del wlp
         _released('block')
-    if not args.no_secondary:
+    if secondary:
         # ---- the same workload with exact-fp32 MFMA convolutions (every rank takes part: the windows hold collectives)
         wl32, b32 = measure(args.workload, device, rank, world, args, barrier, precision="f32")
         result["f32_conv"] = {k: b32[k] for k in ("value", "ms_per_step", "ms_per_scene", "scenes_per_step", "windows_scenes_per_s",
@@ -1075,16 +1161,16 @@ def main():
             _released('block')
         if args.workload != "S":
             wls, bs = measure("S", device, rank, world, args, barrier)
-            if rank == 0 and not args.no_profile:
+            if rank == 0 and profile:
                 bs["roofline"] = profile_block(wls, bs, "S")
             bs["workload"] = "S: ScanNet config shape, V=40, C=32, 120x160 maps (stride 4), grid 192x192x80 (BASELINE configs[1])"
-            if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            if rank == 0 and world == 1 and cpu:
                 log("cpu baseline of the S block")
                 bs["cpu_baseline"] = cpu_baseline("S", bs["M_selected"], 32)
             result["S"] = bs
             del wls
             _released('block')
-    if not args.no_secondary and not args.through_plugin and args.workload != "St":
+    if secondary and not args.through_plugin and args.workload != "St":
         # ---- ScanNet TEST shape (ray_marching_scannet.py:16,19: 50 views, grid 256 x 256 x 96): numbers only
         wlt, bt = measure("St", device, rank, world, args, barrier)
         result["St"] = {k: bt[k] for k in ("value", "ms_per_step", "ms_per_scene", "scenes_per_step", "windows_scenes_per_s",
@@ -1092,7 +1178,7 @@ def main():
         result["St"]["workload"] = "St: ScanNet test shape, V=50, C=32, 120x160 maps (stride 4), grid 256x256x96 (ray_marching_scannet.py:16,19)"
         del wlt
         _released('block')
-    if not args.no_secondary and not args.through_plugin:
+    if secondary and not args.through_plugin:
         # ---- BASELINE configs[2]: the ARKitScenes detector (ray_marching_arkit.py: 17 classes, 8 regression outputs, yaw decode)
         # built from its shipped model section and driven through the plugin API at its own shape (40 views, 192 x 192 x 80)
         try:
@@ -1114,7 +1200,7 @@ def main():
             log(f"A block failed: {e!r}")
             result["A"] = None
         _released('block')
-    if rank == 0 and world == 1 and not args.no_secondary and not args.through_plugin:
+    if rank == 0 and world == 1 and secondary and not args.through_plugin:
         log("training step at the ScanNet shape (bf16 autocast)")
         try:
             result["train_S"] = train_block(device)
@@ -1123,13 +1209,15 @@ def main():
             log(f"train_S failed: {e!r}")
             result["train_S"] = None
         _released('block')
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and cpu:
         name = args.workload if args.workload in ("NS", "S", "St") else "tiny"
         log("cpu baseline (oracle on the host cores)")
         result["cpu_baseline"] = cpu_baseline(name, Ms_full, C)
         log("done")
     if rank == 0:
-        emit(result, args.detail)
+        if not args.full and not args.detail:
+            result["detail"] = None
+        emit(result, args.detail, default_detail=args.full)
     if world > 1:
         dist.destroy_process_group()
 

@@ -111,3 +111,67 @@ def test_roofline_traffic_is_read_from_the_committed_pmc_passes():
     # the dense kernel at NS: ~60 GB per launch against 19.86 GB algorithmic
     assert 40e9 < bench.pmc_traffic("NS", "dense")[0] < 80e9
     assert bench.pmc_traffic("NS", "dense", tag="no_such_round") is None
+
+
+def _graph_workload(batch=False, bad=0):
+    """what dump_outputs() reads of a graph-path workload after its last step: 2 scenes, 2 levels of 4 + 3 padded rows in
+    the step buffers; the slot is a real StaticScene / StaticBatch (its detections() picks the live rows), its outputs
+    hold another scene's block"""
+    import types
+    import torch
+    from cnrma_amd import pipeline
+    det = torch.full((2, 7, 6 + 18), float("nan"))
+    for j in range(2):
+        for r in range(7):
+            det[j, r] = 100 * j + r + torch.arange(24) / 100
+    valid = torch.tensor([[2, 1], [0, 3]], dtype=torch.int32)
+    B = 2 if batch else 1
+    out = dict(sizes=[4, 3], n_levels=2, status=torch.zeros(1, dtype=torch.int32), done=None,
+               counts=torch.zeros(2 * B + B + 2 * 2 * B if batch else 7, dtype=torch.int32),
+               bboxes=torch.zeros((B, 7, 6) if batch else (7, 6)), scores=torch.zeros((B, 7, 18) if batch else (7, 18)),
+               valid=torch.zeros((B, 2) if batch else (2,), dtype=torch.int32))
+    if batch:
+        slot = object.__new__(pipeline.StaticBatch)
+        slot.B, slot.device = B, torch.device("cpu")
+    else:
+        slot = object.__new__(pipeline.StaticScene)
+    slot.out = out
+    return types.SimpleNamespace(torch=torch, plugin=False, args=types.SimpleNamespace(eager=False), det=det, det_valid=valid,
+                                 box_w=6, slots=[slot], sps=2, B=B, violations=lambda: bad)
+
+
+@pytest.fixture
+def cpu_readback(monkeypatch):
+    """the dump on the CPU: no device to synchronise, host reads straight from the tensor"""
+    import torch
+    from cnrma_amd import _lib
+    monkeypatch.setattr(torch.cuda, "synchronize", lambda *a, **k: None)
+    monkeypatch.setattr(_lib, "read_ints", lambda t: t.reshape(-1).tolist())
+
+
+@pytest.mark.parametrize("batch", [False, True])
+def test_dump_outputs_writes_the_live_rows_of_the_last_step(tmp_path, cpu_readback, batch):
+    import numpy as np
+    wl = _graph_workload(batch)
+    bench.dump_outputs(wl, str(tmp_path / "out"))
+    assert sorted(os.listdir(tmp_path / "out")) == ["bboxes.npy", "rows.npy", "scores.npy"]
+    b, s, rows = (np.load(tmp_path / "out" / f"{k}.npy") for k in ("bboxes", "scores", "rows"))
+    assert b.dtype == s.dtype == np.float32 and rows.dtype == np.float64
+    assert rows.tolist() == [[2, 1], [0, 3]] and b.shape == (6, 6) and s.shape == (6, 18)
+    live = [(0, 0), (0, 1), (0, 4), (1, 4), (1, 5), (1, 6)]            # (scene, padded row): level 0 at row 0, level 1 at row 4
+    want = np.stack([wl.det[j, r].numpy() for j, r in live])
+    assert np.array_equal(b, want[:, :6]) and np.array_equal(s, want[:, 6:])
+
+
+def test_dump_outputs_keeps_the_first_scenes_within_the_size_limit(tmp_path, cpu_readback, monkeypatch):
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 3 * 24 * 4 + 16 + 1)     # scene 0 (3 rows) fits, scene 1 does not
+    bench.dump_outputs(_graph_workload(), str(tmp_path / "out"))
+    assert np.load(tmp_path / "out" / "rows.npy").tolist() == [[2, 1]]
+    assert np.load(tmp_path / "out" / "bboxes.npy").shape == (3, 6)
+
+
+def test_dump_outputs_refuses_a_run_that_violated_the_plan(tmp_path, cpu_readback):
+    with pytest.raises(RuntimeError, match="violation"):
+        bench.dump_outputs(_graph_workload(bad=1), str(tmp_path / "out"))
+    assert not (tmp_path / "out").exists()
