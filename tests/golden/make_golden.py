@@ -45,6 +45,16 @@ def scene(shape, seed, boxes=0, origin=(0.0, 0.0, 0.0), V=None):
     return sc
 
 
+def ref_view_rows(fn, *args, **kw):
+    """one view through the reference's ray_projection_neus / _depth the way aggregate_2d_features_ray_marching calls it
+    (ray_marching.py:277-287): an exception skips the view.  A view that keeps exactly one sample raises TypeError
+    (len() of the 0-dim index, :781-782 / :930-931).  Returns (rows or None, skipped)."""
+    try:
+        return fn(*args, **kw), False
+    except TypeError:
+        return None, True
+
+
 def run_scene(rm, tr, name, sc, thr=0.05, n_steps=300, max_points=None, mask_seed=7):
     dims, vs, origin, stride = sc["dims"], sc["voxel_size"], sc["origin"], sc["stride"]
     feats, projs, tsdf = sc["features"], sc["projection"], sc["tsdf"]
@@ -86,7 +96,7 @@ def run_scene(rm, tr, name, sc, thr=0.05, n_steps=300, max_points=None, mask_see
     rows_all, counts = [], []
     for v in range(V):
         ps = O.scale_projection(projs[v], stride)
-        ref = obj.ray_projection_neus(ps, feats[v], tsdf, grids=n_steps, weight_threshold=thr)
+        ref, _ = ref_view_rows(obj.ray_projection_neus, ps, feats[v], tsdf, grids=n_steps, weight_threshold=thr)
         orc, dbg = O.rma_neus_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, n_steps, thr, return_debug=True)
         if ref is None:
             assert orc is None
@@ -112,7 +122,7 @@ def run_scene(rm, tr, name, sc, thr=0.05, n_steps=300, max_points=None, mask_see
     # ---- a6 depth variant, k = 0, 1, 2 (view 0 and scene aggregate for k=1)
     for k in (0, 1, 2):
         ps = O.scale_projection(projs[0], stride)
-        ref = obj.ray_projection_depth(ps, feats[0], tsdf, grids=n_steps, select_grids=k)
+        ref, _ = ref_view_rows(obj.ray_projection_depth, ps, feats[0], tsdf, grids=n_steps, select_grids=k)
         orc = O.rma_depth_view(ps[0], feats[0, 0], tsdf[0, 0], dims, vs, origin, n_steps, k)
         if ref is None:
             assert orc is None
@@ -138,6 +148,157 @@ def run_scene(rm, tr, name, sc, thr=0.05, n_steps=300, max_points=None, mask_see
                vox_coords=Cq.numpy(), vox_src=src.numpy().astype(np.int32))
     np.savez_compressed(os.path.join(HERE, f"rma_{name}.npz"), **out)
     print(f"rma_{name}.npz: V={V} rows/view={counts} points={tuple(pts_ref.shape)} unique={Cq.shape[0]}")
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# views that keep exactly ONE sample: the reference drops them (ray_marching.py:781-782 / :930-931 raise TypeError inside
+# the bare except of :277-287); with no view left it raises TypeError itself (:300)
+# --------------------------------------------------------------------------------------------------------------------
+QUIRK_SHAPE = (3, 4, 30, 40, (48, 48, 20), 4)    # the "tiny" geometry with 4 channels: fixtures well under 100 KB
+
+
+def rays_per_voxel(sc, v, n_steps=300):
+    """int64 [X,Y,Z]: how many rays of view v take a valid sample in each voxel (O.march_samples)"""
+    X, Y, Z = sc["dims"]
+    H, W = sc["features"].shape[-2:]
+    o, d = O.ray_params(O.scale_projection(sc["projection"][v, 0], sc["stride"]), H, W)
+    _, vid, valid, _ = O.march_samples(o, d, sc["tsdf"][0, 0], sc["dims"], sc["voxel_size"], sc["origin"], n_steps)
+    lin = (vid[0] * Y + vid[1]) * Z + vid[2]
+    ray = torch.arange(lin.shape[0]).view(-1, 1).expand_as(lin)
+    pairs = torch.unique(torch.stack((lin[valid], ray[valid])), dim=1)
+    return torch.bincount(pairs[0], minlength=X * Y * Z).view(X, Y, Z)
+
+
+def single_voxel(n_target, others=()):
+    """linear id of a voxel sampled by exactly one ray of the target view (and by no ray of `others`): the middle one"""
+    ok = n_target == 1
+    for n in others:
+        ok &= n == 0
+    ids = torch.nonzero(ok.view(-1))[:, 0]
+    return int(ids[ids.numel() // 2])
+
+
+def quirk_neus_scene(target):
+    """NeuS: the room of "tiny" (seed 4, 3 boxes) with every voxel that view `target` samples set to +1 except one voxel
+    that exactly one of its rays samples, set to -1: that ray keeps one sample (alpha > 0 where it leaves the voxel), no
+    other ray of the view keeps any -- the other views keep hundreds"""
+    sc = synth.make_scene(QUIRK_SHAPE, seed=4, boxes=3, V=3)
+    sc["features"] = torch.round(sc["features"] * 8) / 8          # values on a 1/8 grid: the fixture compresses well
+    n = rays_per_voxel(sc, target)
+    t = sc["tsdf"][0, 0]
+    t.copy_(torch.round(t * 64) / 64)                              # and the TSDF on a 1/64 grid
+    t[n > 0] = 1.0
+    t.view(-1)[single_voxel(n)] = -1.0
+    return sc
+
+
+def quirk_depth_scene():
+    """depth (select_grids = 0): TSDF +1 everywhere but a -1 block that only view 1 samples (its rays hit) and one -1 voxel
+    that exactly one ray of view 0 and no ray of the others samples: view 0 keeps one row, views 1 and 2 keep hundreds"""
+    sc = synth.make_scene(QUIRK_SHAPE, seed=6, V=3)
+    sc["features"] = torch.round(sc["features"] * 8) / 8
+    n0, n1, n2 = (rays_per_voxel(sc, v) for v in range(3))
+    t = sc["tsdf"][0, 0]
+    t.fill_(1.0)
+    cand = (n1 > 0) & (n0 == 0)
+    cx, cy, _ = torch.nonzero(cand).float().median(dim=0).values.long().tolist()
+    box = torch.zeros_like(cand)
+    box[max(0, cx - 3):cx + 3, max(0, cy - 3):cy + 3, :] = True
+    t[cand & box] = -1.0
+    t.view(-1)[single_voxel(n0, (n1, n2))] = -1.0
+    return sc
+
+
+def run_quirk_scene(rm, name, sc, thr=0.05, n_steps=300):
+    """per view (NeuS, depth k = 0, 1, 2): the reference's rows, which views it skipped, and the one-row block of each
+    skipped view from the oracle's pre-skip path (the product's rma_view_rows has no quirk and returns it); the scene
+    aggregate of the reference's own aggregate_2d_features_ray_marching per mode, or a flag when it raises TypeError"""
+    dims, vs, origin, stride = sc["dims"], sc["voxel_size"], sc["origin"], sc["stride"]
+    feats, projs, tsdf = sc["features"], sc["projection"], sc["tsdf"]
+    V, C = feats.shape[0], feats.shape[2]
+    out = dict(features=feats[:, 0].numpy(), projection=projs[:, 0].numpy(), tsdf=tsdf[0, 0].numpy(),
+               dims=np.array(dims), voxel_size=np.float64(vs), origin=np.array(origin, dtype=np.float32),
+               stride=np.int64(stride), thr=np.float64(thr), n_steps=np.int64(n_steps),
+               proj_inv=np.stack([O.projection_inverse(O.scale_projection(projs[v, 0], stride)).numpy() for v in range(V)]))
+    summary = {}
+    for mode, k in (("neus", None), ("depth", 0), ("depth", 1), ("depth", 2)):
+        tag = "neus" if mode == "neus" else f"depth_k{k}"
+        obj = R.make_raymarching(rm, dims, vs, origin, stride, rtype=mode, thr=thr, depth_points=k)
+        rows, counts, skipped, single = [], [], [], []
+        for v in range(V):
+            ps = O.scale_projection(projs[v], stride)
+            if mode == "neus":
+                ref, skip = ref_view_rows(obj.ray_projection_neus, ps, feats[v], tsdf, grids=n_steps, weight_threshold=thr)
+                orc = O.rma_neus_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, n_steps, thr)
+                raw = O.rma_neus_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, n_steps, thr, reference_quirks=False)
+            else:
+                ref, skip = ref_view_rows(obj.ray_projection_depth, ps, feats[v], tsdf, grids=n_steps, select_grids=k)
+                orc = O.rma_depth_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, n_steps, k)
+                raw = O.rma_depth_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, n_steps, k, reference_quirks=False)
+            if skip:                                   # the reference raised: the oracle drops the view, one raw row
+                assert orc is None and raw is not None and raw.shape[0] == 1, (tag, v)
+                single.append(raw.numpy())
+            elif ref is None:
+                assert orc is None and raw is None
+            else:
+                eq(orc, ref[0], f"{tag} rows view {v}")
+                rows.append(ref[0].numpy())
+            counts.append(0 if ref is None else ref[0].shape[0])
+            skipped.append(skip)
+        out[f"{tag}_counts"] = np.array(counts, dtype=np.int64)
+        out[f"{tag}_skipped"] = np.array(skipped)
+        out[f"{tag}_rows"] = np.concatenate(rows) if rows else np.zeros((0, 4 + C), np.float32)
+        out[f"{tag}_single_rows"] = np.concatenate(single) if single else np.zeros((0, 4 + C), np.float32)
+        # the scene aggregate, from the reference's own loop
+        obj.points_detection = []
+        try:
+            obj.aggregate_2d_features_ray_marching(projs, feats, tsdf)
+            pts_ref = obj.points_detection[0]
+        except TypeError:
+            pts_ref = None
+        if pts_ref is None:
+            try:
+                O.aggregate_rma(projs[:, 0], feats[:, 0], tsdf[0, 0], dims, vs, origin, stride, n_steps, thr, mode, k or 0)
+                raise AssertionError(f"{tag}: the oracle aggregates a scene the reference rejects")
+            except TypeError:
+                pass
+            out[f"{tag}_raises"] = np.bool_(True)
+            out[f"{tag}_points"] = np.zeros((0, 3 + C), np.float32)
+        else:
+            pts_or = O.aggregate_rma(projs[:, 0], feats[:, 0], tsdf[0, 0], dims, vs, origin, stride, n_steps, thr, mode, k or 0)
+            eq(pts_or, pts_ref, f"{tag} aggregate points")
+            out[f"{tag}_raises"] = np.bool_(False)
+            out[f"{tag}_points"] = pts_ref.numpy()
+        summary[tag] = [("skip" if s_ else c) for c, s_ in zip(counts, skipped)] + (["raises"] if pts_ref is None else [])
+    path = os.path.join(HERE, f"rma_{name}.npz")
+    np.savez_compressed(path, **out)
+    print(f"rma_{name}.npz: V={V} {summary} ({os.path.getsize(path)} bytes)")
+
+
+def run_quirk_single_view(rm, name, sc, thr=0.05, n_steps=300):
+    """one view that keeps exactly one sample: the reference's aggregate_2d_features_ray_marching raises TypeError (:300,
+    no view left).  Only the inputs and that flag are saved."""
+    dims, vs, origin, stride = sc["dims"], sc["voxel_size"], sc["origin"], sc["stride"]
+    feats, projs, tsdf = sc["features"][:1], sc["projection"][:1], sc["tsdf"]
+    obj = R.make_raymarching(rm, dims, vs, origin, stride, thr=thr)
+    obj.points_detection = []
+    try:
+        obj.aggregate_2d_features_ray_marching(projs, feats, tsdf)
+        raises = False
+    except TypeError:
+        raises = True
+    assert raises, "the reference aggregated a scene whose only view keeps one sample"
+    raw = O.rma_neus_view(O.scale_projection(projs[0, 0], stride), feats[0, 0], tsdf[0, 0], dims, vs, origin, n_steps, thr,
+                          reference_quirks=False)
+    assert raw is not None and raw.shape[0] == 1
+    out = dict(features=feats[:, 0].numpy(), projection=projs[:, 0].numpy(), tsdf=tsdf[0, 0].numpy(),
+               dims=np.array(dims), voxel_size=np.float64(vs), origin=np.array(origin, dtype=np.float32),
+               stride=np.int64(stride), thr=np.float64(thr), n_steps=np.int64(n_steps),
+               proj_inv=O.projection_inverse(O.scale_projection(projs[0, 0], stride)).numpy()[None],
+               neus_raises=np.bool_(raises))
+    path = os.path.join(HERE, f"rma_{name}.npz")
+    np.savez_compressed(path, **out)
+    print(f"rma_{name}.npz: V=1 raises TypeError ({os.path.getsize(path)} bytes)")
 
 
 def run_decode(head_mod):
@@ -250,6 +411,10 @@ def main():
     P = sc["projection"]
     P[0, 0, :, :3] = -P[0, 0, :, :3]            # mirror the camera through its centre: every ray leaves the grid
     run_scene(rm, tr, "edge_empty_view", sc)
+    run_quirk_scene(rm, "edge_single_sample", quirk_neus_scene(0))
+    run_quirk_scene(rm, "edge_single_sample_v1", quirk_neus_scene(1))
+    run_quirk_scene(rm, "edge_single_sample_depth", quirk_depth_scene())
+    run_quirk_single_view(rm, "edge_single_sample_only", quirk_neus_scene(0))
     run_decode(head)
     run_point_transforms(tr)
     run_atlas3d()
@@ -258,6 +423,14 @@ def main():
 
 if __name__ == "__main__" and "--backbone2d" in sys.argv:
     run_backbone2d()
+    sys.exit(0)
+
+if __name__ == "__main__" and "--quirks" in sys.argv:
+    _rm = R.load_reference()[0]
+    run_quirk_scene(_rm, "edge_single_sample", quirk_neus_scene(0))
+    run_quirk_scene(_rm, "edge_single_sample_v1", quirk_neus_scene(1))
+    run_quirk_scene(_rm, "edge_single_sample_depth", quirk_depth_scene())
+    run_quirk_single_view(_rm, "edge_single_sample_only", quirk_neus_scene(0))
     sys.exit(0)
 
 if __name__ == "__main__" and "--atlas3d" in sys.argv:

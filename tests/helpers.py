@@ -6,6 +6,11 @@ import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SCENES = ["tiny", "tiny_boxes_origin", "mini_p", "edge_empty_view"]
+# scenes in which a view keeps exactly one sample and the reference drops it (ray_marching.py:781-782 / :930-931 inside the
+# bare except of :277-287): their fixtures hold per-view rows only for the views the reference kept, so they are not in
+# SCENES; dedicated tests use them (make_golden.py run_quirk_scene)
+QUIRK_SCENES = ["edge_single_sample", "edge_single_sample_v1", "edge_single_sample_depth"]
+QUIRK_SINGLE_VIEW = "edge_single_sample_only"      # its one view keeps one sample: the reference raises TypeError (:300)
 
 
 def load_golden(name):

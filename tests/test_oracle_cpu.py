@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import SCENES, bits_equal, count_mismatch, load_golden, t
+from helpers import QUIRK_SCENES, QUIRK_SINGLE_VIEW, SCENES, bits_equal, count_mismatch, load_golden, t
 from oracle import rma_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -93,6 +93,114 @@ def test_all_views_empty_raises_like_reference():
     with pytest.raises(TypeError):
         O.aggregate_rma(t(g["projection"][:1]), t(g["features"][:1]), t(g["tsdf"]), g["dims"], g["voxel_size"],
                         g["origin"], g["stride"])
+
+
+QUIRK_MODES = [("neus", None), ("depth", 0), ("depth", 1), ("depth", 2)]
+
+
+@pytest.mark.parametrize("name", QUIRK_SCENES)
+@pytest.mark.parametrize("mode,k", QUIRK_MODES)
+def test_oracle_drops_single_sample_views_like_reference(name, mode, k):
+    """a view that keeps exactly one sample is skipped by the reference (ray_marching.py:781-782 / :930-931 raise inside
+    the bare except of :277-287): per-view rows, skipped views and the scene aggregate of the reference's own loop"""
+    g = load_golden(name)
+    tag = "neus" if mode == "neus" else f"depth_k{k}"
+    tsdf = t(g["tsdf"])
+    rows, raw_single = [], []
+    for v in range(g["features"].shape[0]):
+        args = (O.scale_projection(t(g["projection"][v]), g["stride"]), t(g["features"][v]), tsdf, g["dims"],
+                g["voxel_size"], g["origin"], g["n_steps"])
+        if mode == "neus":
+            r = O.rma_neus_view(*args, g["thr"])
+            raw = O.rma_neus_view(*args, g["thr"], reference_quirks=False)
+        else:
+            r = O.rma_depth_view(*args, k)
+            raw = O.rma_depth_view(*args, k, reference_quirks=False)
+        if g[f"{tag}_skipped"][v]:
+            assert r is None and raw is not None and raw.shape[0] == 1, v
+            raw_single.append(raw)
+        else:
+            assert (0 if r is None else r.shape[0]) == g[f"{tag}_counts"][v], v
+            if r is not None:
+                assert count_mismatch(r, raw) == 0
+                rows.append(r)
+    exp_rows = g[f"{tag}_rows"]
+    assert count_mismatch(torch.cat(rows) if rows else torch.zeros(exp_rows.shape), exp_rows) == 0
+    exp_single = g[f"{tag}_single_rows"]
+    assert len(raw_single) == exp_single.shape[0] == int(g[f"{tag}_skipped"].sum())
+    if raw_single:
+        assert count_mismatch(torch.cat(raw_single), exp_single) == 0
+    agg = (t(g["projection"]), t(g["features"]), tsdf, g["dims"], g["voxel_size"], g["origin"], g["stride"], g["n_steps"],
+           g["thr"], mode, k or 0)
+    if g[f"{tag}_raises"]:
+        with pytest.raises(TypeError):
+            O.aggregate_rma(*agg)
+    else:
+        pts = O.aggregate_rma(*agg)
+        assert count_mismatch(pts, g[f"{tag}_points"]) == 0
+    # without the quirk the one-sample views come back: exactly one row more per skipped view
+    if raw_single:
+        full = O.aggregate_rma(*agg, reference_quirks=False)
+        assert full.shape[0] == g[f"{tag}_points"].shape[0] + len(raw_single)
+
+
+def test_quirk_fixtures_hold_the_cases_they_are_for():
+    """the fixtures exercise what they are named for: a one-sample view among views that keep many, at view 0 and at
+    view 1 (NeuS), and at view 0 in depth mode k = 0; for k >= 1 a hit ray emits >= 2 rows, so nothing is dropped"""
+    a, b, d = (load_golden(n) for n in QUIRK_SCENES)
+    assert list(a["neus_skipped"]) == [True, False, False] and min(a["neus_counts"][1:]) >= 100
+    assert list(b["neus_skipped"]) == [False, True, False] and min(b["neus_counts"][[0, 2]]) >= 100
+    assert list(d["depth_k0_skipped"]) == [True, False, False] and min(d["depth_k0_counts"][1:]) >= 50
+    for g in (a, b, d):
+        assert not g["depth_k1_skipped"].any() and not g["depth_k2_skipped"].any()
+
+
+def test_single_view_of_one_sample_raises_like_reference():
+    g = load_golden(QUIRK_SINGLE_VIEW)
+    assert bool(g["neus_raises"]) and g["features"].shape[0] == 1
+    args = (t(g["projection"]), t(g["features"]), t(g["tsdf"]), g["dims"], g["voxel_size"], g["origin"], g["stride"],
+            g["n_steps"], g["thr"])
+    with pytest.raises(TypeError):
+        O.aggregate_rma(*args)
+    assert O.aggregate_rma(*args, reference_quirks=False).shape[0] == 1
+
+
+def _voxel_subset_cases():
+    for name in SCENES + QUIRK_SCENES:
+        g = load_golden(name)
+        yield name, g["dims"], g["voxel_size"], g["origin"], t(g["projection"]), t(g["features"]), g["stride"]
+
+
+@pytest.mark.parametrize("case", ["golden", "ragged"])
+def test_backproject_voxels_equal_full_grid_bit_for_bit(case):
+    """backproject_voxels / backproject_accum_voxels (the oracle of the north-star-size dense test, which samples voxels)
+    == backproject_view / backproject_accum at every voxel, bit for bit: on every fixture, and on a grid whose bricks of
+    16 x 16 x 32 are ragged (72 x 100 x 80); the gather-callable form gives the same values"""
+    from cnrma_amd import synth
+    if case == "golden":
+        cases = list(_voxel_subset_cases())
+    else:
+        sc = synth.make_scene((6, 32, 60, 80, (72, 100, 80), 4), seed=4)
+        cases = [("ragged", sc["dims"], sc["voxel_size"], sc["origin"], sc["projection"][:, 0], sc["features"][:, 0],
+                  sc["stride"])]
+    for name, dims, vs, origin, proj, feat, stride in cases:
+        G = dims[0] * dims[1] * dims[2]
+        gidx = torch.arange(G)
+        vol, cnt = O.backproject_accum(dims, vs, origin, proj, feat, stride)
+        vol2, cnt2 = O.backproject_accum_voxels(dims, vs, origin, proj, feat, stride, gidx)
+        assert torch.equal(cnt.view(-1), cnt2), name
+        assert count_mismatch(vol.view(vol.shape[0], -1), vol2) == 0, name
+        assert int(cnt.max()) > 0
+        ps = O.scale_projection(proj[0], stride)
+        v0, ok0, px0, py0 = O.backproject_view(dims, vs, origin, ps, feat[0])
+        perm = torch.randperm(G, generator=torch.Generator().manual_seed(1))[: G // 3]
+        v1, ok1, px1, py1 = O.backproject_voxels(dims, vs, origin, ps, feat[0], perm)
+        assert torch.equal(ok1, ok0[perm]) and torch.equal(px1, px0[perm]) and torch.equal(py1, py0[perm])
+        assert count_mismatch(v1, v0[:, perm]) == 0
+        H, W = feat.shape[-2:]
+        gathers = [(lambda f: (lambda py, px: f[:, py, px]))(feat[v]) for v in range(feat.shape[0])]
+        vol3, cnt3 = O.backproject_accum_voxels(dims, vs, origin, proj, gathers, stride, perm, hw=(H, W))
+        assert torch.equal(cnt3, cnt.view(-1)[perm]) and count_mismatch(vol3, vol.view(vol.shape[0], -1)[:, perm]) == 0
 
 
 def test_host_projection_inverse_matches_golden():

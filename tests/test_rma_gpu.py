@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import SCENES, bits_equal, count_mismatch, load_golden, t
+from helpers import QUIRK_SCENES, QUIRK_SINGLE_VIEW, SCENES, bits_equal, count_mismatch, load_golden, t
 
 pytestmark = pytest.mark.gpu
 
@@ -480,3 +480,220 @@ def test_device_scans_match_torch_on_both_sides_of_the_single_launch_threshold(d
     rank = torch.cumsum(mask.long(), 0) - mask.long()
     assert int(n_sel) == int(mask.sum())
     assert torch.equal(sel.long(), torch.where(mask.bool(), rank, torch.full_like(rank, -1)))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# views that keep exactly one sample (ray_marching.py:781-782 / :930-931 inside the bare except of :277-287):
+# cnrma_rma_drop_single_sample_views against a numpy model, then the eager aggregation against the reference's fixtures
+# ---------------------------------------------------------------------------------------------------------------------
+_DROP_CASES = ("zero", "one_first", "one_last", "one_middle", "two_split", "two_one_ray", "large")
+
+
+def _drop_view_counts(case, rpv, rng):
+    c = np.zeros(rpv, dtype=np.int32)
+    if case == "one_first":
+        c[0] = 1
+    elif case == "one_last":
+        c[-1] = 1
+    elif case == "one_middle":
+        c[rpv // 2] = 1
+    elif case == "two_split":
+        if rpv == 1:
+            c[0] = 2
+        else:
+            c[rpv // 3] = 1
+            c[-1] = 1
+    elif case == "two_one_ray":
+        c[(rpv * 2) // 3] = 2
+    elif case == "large":
+        c[:] = rng.randint(0, 6, size=rpv)
+        c[rpv // 2] += 7
+    return c
+
+
+@pytest.mark.parametrize("offset", [0, 1])
+@pytest.mark.parametrize("V", [1, 3, 40])
+@pytest.mark.parametrize("rpv", [1, 3, 1023, 1024, 1025, 4095, 4096, 4097, 4100, 120 * 160, 480 * 640])
+def test_drop_single_sample_views_kernel_vs_model(device, rpv, V, offset):
+    """count / wsum of the views whose total is exactly 1 are zeroed, every other element -- and canaries on both sides of the
+    range -- is bit-unchanged; the int4 path (rays_per_view % 4 == 0 on a 16-byte aligned base) and the scalar path
+    (ragged rays_per_view, or a base one element off alignment); every per-view case at every view position"""
+    from cnrma_amd._lib import call, ptr, stream
+    rng = np.random.RandomState(rpv * 7 + V * 3 + offset)
+    pre, post = 8 + offset, 8
+    n = V * rpv
+    for shift in range(len(_DROP_CASES) if V < len(_DROP_CASES) else 1):
+        cases = [_DROP_CASES[(v + shift) % len(_DROP_CASES)] for v in range(V)]
+        cnt = np.concatenate([_drop_view_counts(c, rpv, rng) for c in cases])
+        wsum = rng.rand(n) * (cnt > 0)
+        wsum[rng.rand(n) < 0.01] = 0.25                       # weight sums on rays without kept samples are left alone too
+        cbuf = rng.randint(-3, 4, size=pre + n + post).astype(np.int32)      # canaries: anything, ones included
+        wbuf = rng.rand(pre + n + post)
+        cbuf[pre:pre + n], wbuf[pre:pre + n] = cnt, wsum
+        cdev, wdev = t(cbuf, device), t(wbuf, device)
+        base_c, base_w = cdev[pre:], wdev[pre:]
+        assert (base_c.data_ptr() % 16 == 0) == (offset == 0)
+        call("cnrma_rma_drop_single_sample_views", base_c.data_ptr(), base_w.data_ptr(), V, rpv, stream())
+        exp_c, exp_w = cbuf.copy(), wbuf.copy()
+        tot = cnt.reshape(V, rpv).sum(axis=1)
+        for v in np.nonzero(tot == 1)[0]:
+            exp_c[pre + v * rpv:pre + (v + 1) * rpv] = 0
+            exp_w[pre + v * rpv:pre + (v + 1) * rpv] = 0.0
+        got_c, got_w = cdev.cpu().numpy(), wdev.cpu().numpy()
+        assert (got_c == exp_c).all(), (cases, np.nonzero(got_c != exp_c)[0][:8])
+        assert (got_w.view(np.uint64) == exp_w.view(np.uint64)).all(), (cases, np.nonzero(got_w != exp_w)[0][:8])
+        assert (tot == 1).any() == any(c.startswith("one") for c in cases)
+
+
+def test_drop_single_sample_views_rejects_bad_arguments(device):
+    from cnrma_amd import _lib
+    from cnrma_amd._lib import call, ptr, stream
+    c = torch.ones(8, dtype=torch.int32, device=device)
+    w = torch.ones(8, dtype=torch.float64, device=device)
+    for args in ((ptr(c), ptr(w), 0, 8), (ptr(c), ptr(w), -1, 8), (ptr(c), ptr(w), 1, 0), (ptr(c), ptr(w), 1, -4),
+                 (None, ptr(w), 1, 8), (ptr(c), None, 1, 8)):
+        with pytest.raises(_lib.CnrmaError, match="invalid argument"):
+            call("cnrma_rma_drop_single_sample_views", *args, stream())
+    torch.cuda.synchronize()
+    assert int(c.sum()) == 8 and float(w.sum()) == 8.0
+
+
+_QUIRK_MODES = [("neus", None), ("depth", 0), ("depth", 1), ("depth", 2)]
+
+
+@pytest.mark.parametrize("name", QUIRK_SCENES)
+@pytest.mark.parametrize("mode,k", _QUIRK_MODES)
+def test_single_sample_view_drop_eager_vs_reference(device, name, mode, k):
+    """rma_view_rows (no quirk) still returns the one row of a view the reference drops; the aggregation (quirk on) returns
+    the reference's points and M, and exactly one row more per dropped view with reference_quirks=False"""
+    from cnrma_amd import rma
+    g = load_golden(name)
+    tag = "neus" if mode == "neus" else f"depth_k{k}"
+    feats, pinv, tsdf = _scene(g, device)
+    kw = dict(mode=mode, select_grids=k or 0)
+    rows, per_view = rma.rma_view_rows(feats, pinv, tsdf, g["dims"], g["voxel_size"], g["origin"], g["n_steps"], g["thr"], **kw)
+    skipped = g[f"{tag}_skipped"]
+    per_view = per_view.cpu().numpy()
+    assert list(per_view) == [1 if s else int(c) for s, c in zip(skipped, g[f"{tag}_counts"])]
+    rows = rows.cpu().numpy()
+    start = np.concatenate(([0], np.cumsum(per_view)))
+    single = np.concatenate([rows[start[v]:start[v + 1]] for v in range(len(skipped)) if skipped[v]] or [rows[:0]])
+    kept = np.concatenate([rows[start[v]:start[v + 1]] for v in range(len(skipped)) if not skipped[v]] or [rows[:0]])
+    for got, exp in ((single, g[f"{tag}_single_rows"]), (kept, g[f"{tag}_rows"])):
+        assert got.shape == exp.shape
+        assert count_mismatch(got[:, :3], exp[:, :3]) == 0 and count_mismatch(got[:, 4:], exp[:, 4:]) == 0
+        np.testing.assert_allclose(got[:, 3], exp[:, 3], rtol=1e-6, atol=0)
+    n_drop = int(skipped.sum())
+    agg = (feats, pinv, tsdf, g["dims"], g["voxel_size"], g["origin"], g["n_steps"], g["thr"])
+    if g[f"{tag}_raises"]:
+        with pytest.raises(TypeError):
+            rma.aggregate_rows(*agg, **kw)
+    else:
+        exp = g[f"{tag}_points"]
+        pts, info = rma.aggregate_rows(*agg, **kw)
+        assert info["M"] == exp.shape[0]
+        pts = pts.cpu().numpy()
+        assert count_mismatch(pts[:, :3], exp[:, :3]) == 0
+        np.testing.assert_allclose(pts[:, 3:], exp[:, 3:], rtol=2e-6, atol=1e-7)
+    _, info = rma.aggregate_rows(*agg, reference_quirks=False, **kw)
+    assert n_drop >= (1 if tag in ("neus", "depth_k0") else 0)
+    assert info["M"] == g[f"{tag}_points"].shape[0] + n_drop
+
+
+def test_single_view_of_one_sample_raises_like_reference(device):
+    from cnrma_amd import rma
+    g = load_golden(QUIRK_SINGLE_VIEW)
+    feats, pinv, tsdf = _scene(g, device)
+    agg = (feats, pinv, tsdf, g["dims"], g["voxel_size"], g["origin"], g["n_steps"], g["thr"])
+    with pytest.raises(TypeError):
+        rma.aggregate_rows(*agg)
+    _, info = rma.aggregate_rows(*agg, reference_quirks=False)
+    assert info["M"] == 1
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the dense unprojection at the north-star size (40 views x 256 ch x 480x640 -> 192^3) against the oracle on a voxel sample
+# ---------------------------------------------------------------------------------------------------------------------
+def _dense_sample(dims, brick=(16, 16, 32), n_random=60000, seed=0):
+    """linear voxel ids: the first, the last and one interior brick whole; both planes of every brick boundary along a
+    cross of lines per axis; the 8 corners and a strip of each face; the rest uniformly random"""
+    X, Y, Z = dims
+    bx, by, bz = brick
+    lin = lambda x, y, z: (np.asarray(x) * Y + np.asarray(y)) * Z + np.asarray(z)
+    parts = []
+    nb = (-(-X // bx), -(-Y // by), -(-Z // bz))
+    for b in ((0, 0, 0), (nb[0] - 1, nb[1] - 1, nb[2] - 1), (nb[0] // 2 - 1, nb[1] // 2, nb[2] // 2)):
+        x, y, z = np.meshgrid(np.arange(b[0] * bx, min(X, b[0] * bx + bx)), np.arange(b[1] * by, min(Y, b[1] * by + by)),
+                              np.arange(b[2] * bz, min(Z, b[2] * bz + bz)), indexing="ij")
+        parts.append(lin(x, y, z).ravel())
+    ext, size = (X, Y, Z), (bx, by, bz)
+    for a in range(3):
+        planes = sorted({c for b in range(size[a], ext[a], size[a]) for c in (b - 1, b)})
+        o1, o2 = [i for i in range(3) if i != a]
+        for c in planes:
+            for vary, fixed in ((o1, o2), (o2, o1)):
+                coord = [None] * 3
+                coord[a] = np.full(ext[vary], c)
+                coord[vary] = np.arange(ext[vary])
+                coord[fixed] = np.full(ext[vary], ext[fixed] // 2 + 3)
+                parts.append(lin(*coord))
+    corners = np.array([[x, y, z] for x in (0, X - 1) for y in (0, Y - 1) for z in (0, Z - 1)])
+    parts.append(lin(corners[:, 0], corners[:, 1], corners[:, 2]))
+    for a in range(3):
+        o1, o2 = [i for i in range(3) if i != a]
+        for c in (0, ext[a] - 1):
+            u, w = np.meshgrid(np.arange(ext[o1]), np.arange(ext[o2] // 2 - 2, ext[o2] // 2 + 2), indexing="ij")
+            coord = [None] * 3
+            coord[a], coord[o1], coord[o2] = np.full(u.size, c), u.ravel(), w.ravel()
+            parts.append(lin(*coord))
+    rng = np.random.RandomState(seed)
+    parts.append(rng.randint(0, X * Y * Z, size=n_random))
+    return np.unique(np.concatenate(parts).astype(np.int64))
+
+
+def test_dense_north_star_shape_vs_oracle_sample(device):
+    """the dominant kernel at the shipped size -- default brick order over 12 x 12 x 6 bricks, 8 sweeps of 32 channels, 40
+    views -- and its channels-last by-reference form (the plugin's hand-off) against the oracle on > 1e5 sampled voxels x 256
+    channels: counts equal, volume bit-equal.  The oracle's pixel indices are computed on the host; the feature values it
+    needs are gathered on the device by plain indexing (an exact copy), view by view.  Accumulating two views in the other
+    order must break bit equality somewhere in the sample: the check sees the fp32 summation order"""
+    import time
+    from cnrma_amd import rma, synth
+    from oracle import rma_oracle as O
+    if torch.cuda.get_device_properties(0).total_memory < 64e9:
+        pytest.skip("needs ~26 GB of device memory (peak measured on an MI355X)")
+    t0 = time.time()
+    torch.cuda.reset_peak_memory_stats()
+    sc = synth.make_scene("NS", seed=3, boxes=3, device=device)
+    dims, stride, origin = sc["dims"], sc["stride"], sc["origin"]
+    proj = sc["projection"][:, 0]
+    nhwc = rma.to_nhwc(sc["features"][:, 0])
+    del sc
+    V, H, W, C = nhwc.shape
+    assert (V, C, H, W, tuple(dims)) == (40, 256, 480, 640, (192, 192, 192))
+    vol, cnt = rma.backproject_accum(nhwc, proj, dims, 0.04, origin, stride)
+    feat_ref = torch.tensor([nhwc.data_ptr()], dtype=torch.int64, device=device)
+    vol_r, cnt_r = rma.backproject_accum(None, proj, dims, 0.04, origin, stride, feat_ref=feat_ref, shape=(V, H, W, C))
+    gidx = _dense_sample(dims)
+    assert gidx.size >= 100_000
+    gi = torch.from_numpy(gidx).to(device)
+    got = [(v.view(C, -1)[:, gi].cpu(), c.view(-1)[gi].cpu().long()) for v, c in ((vol, cnt), (vol_r, cnt_r))]
+    del vol, vol_r, cnt, cnt_r
+    gathers = [(lambda f: (lambda py, px: f[py.to(device), px.to(device)].t().cpu()))(nhwc[v]) for v in range(V)]
+    exp_v, exp_c = O.backproject_accum_voxels(dims, 0.04, origin, proj, gathers, stride, torch.from_numpy(gidx), hw=(H, W))
+    for path, (gv, gc) in zip(("nhwc", "by reference"), got):
+        assert torch.equal(gc, exp_c), path
+        assert count_mismatch(gv, exp_v) == 0, path
+    hist = np.bincount(exp_c.numpy(), minlength=V + 1)
+    print(f"\nNS dense: {gidx.size} sampled voxels x {C} channels; views per voxel histogram {hist.tolist()}")
+    assert hist[0] > 0 and hist[V // 2:].sum() > 0
+    # negative control: the last two views swapped on the oracle side (a 20 000-voxel part of the sample)
+    part = torch.from_numpy(gidx[::max(1, gidx.size // 20000)])
+    sel = torch.from_numpy(np.searchsorted(gidx, part.numpy()))
+    sw_v, sw_c = O.backproject_accum_voxels(dims, 0.04, origin, proj, gathers, stride, part, hw=(H, W),
+                                            order=list(range(V - 2)) + [V - 1, V - 2])
+    assert torch.equal(sw_c, exp_c[sel])
+    assert count_mismatch(got[0][0][:, sel], sw_v) > 0
+    print(f"NS dense: peak device memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB, {time.time() - t0:.1f} s")
+    del nhwc, gathers, feat_ref
+    torch.cuda.empty_cache()

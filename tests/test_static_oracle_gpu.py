@@ -7,7 +7,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import SCENES, count_mismatch, elementwise_error, load_golden, t
+from helpers import QUIRK_SCENES, QUIRK_SINGLE_VIEW, SCENES, count_mismatch, elementwise_error, load_golden, t
 from oracle import rma_oracle as RO
 from oracle import sparse_oracle as SO
 
@@ -170,3 +170,100 @@ def test_run_orders_itself_behind_the_producer_stream(device):
         b, s, info = pipeline.StaticScene.detections(out)
         assert torch.equal(out["volume"], ref_vol) and torch.equal(b, ref_b)
         del scratch
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# views that keep exactly one sample inside the captured scene (rma.aggregate_points_static -> cnrma_rma_drop_single_sample_views)
+# ---------------------------------------------------------------------------------------------------------------------
+def _oracle_scene(g, tsdf, mode="neus", k=0):
+    """dense volume / count and aggregated points of the oracle (pinned to the reference by the golden tests), with the
+    fixture's inverse projections as inputs -- the same ones the slot is given"""
+    proj, feat = t(g["projection"]), t(g["features"])
+    vol, cnt = RO.backproject_accum(g["dims"], g["voxel_size"], g["origin"], proj, feat, g["stride"])
+    pts = RO.aggregate_rma(proj, feat, tsdf, g["dims"], g["voxel_size"], g["origin"], g["stride"], g["n_steps"], g["thr"],
+                           mode, k, proj_inv=t(g["proj_inv"]))
+    return vol, cnt, pts.numpy()
+
+
+def _check_static_scene(out, vol, cnt, pts):
+    b, s, info = _detections(out)
+    assert (out["count"].cpu().long() == cnt).all()
+    assert count_mismatch(out["volume"], vol) == 0
+    coords, _, n_sel = out["points"]
+    n = pts.shape[0]
+    assert info["M"] == n == int(n_sel) == info["M_selected"]
+    assert count_mismatch(coords[:n], pts[:, :3]) == 0
+    from cnrma_amd import pipeline
+    pf = pipeline.StaticScene.point_features(out)
+    np.testing.assert_allclose(pf[:n].cpu().numpy(), pts[:, 3:], rtol=2e-6, atol=1e-7)
+
+
+def _detections(out):
+    from cnrma_amd import pipeline
+    return pipeline.StaticScene.detections(out)
+
+
+@pytest.mark.parametrize("name,mode,k", [(n, "neus", 0) for n in QUIRK_SCENES] + [("edge_single_sample_depth", "depth", 0)])
+def test_graph_replay_drops_single_sample_views_like_reference(device, name, mode, k):
+    """the captured scene on the fixtures with a view that keeps one sample: count, volume, places and deferred point
+    features equal the reference's (its points) on the first replay and on a replay after another scene went through the
+    graph; that other scene -- the same views over the TSDF mirrored in x, no one-sample view -- is unaffected"""
+    from cnrma_amd import pipeline
+    g = load_golden(name)
+    tag = "neus" if mode == "neus" else f"depth_k{k}"
+    assert g[f"{tag}_skipped"].any() and not g[f"{tag}_raises"]
+    feat, proj, pinv = t(g["features"], device), t(g["projection"]), t(g["proj_inv"])
+    tsdf = t(g["tsdf"])
+    other = tsdf.flip(0).contiguous()
+    vol, cnt, _ = _oracle_scene(g, tsdf, mode, k)
+    exp = g[f"{tag}_points"]
+    _, _, pts_other = _oracle_scene(g, other, mode, k)
+    assert pts_other.shape[0] > exp.shape[0]
+    backbone, head = _model(feat.shape[1], device)
+    cfg = pipeline.SceneConfig(g["dims"], voxel_size=g["voxel_size"], origin=g["origin"], stride=g["stride"],
+                               n_steps=g["n_steps"], thr=g["thr"], max_points=500000, sample_seed=11,
+                               ray_marching_type=mode, depth_points=k)
+    st = pipeline.StaticScene(cfg, backbone, head, device)
+    st.build(feat, proj, other.to(device), proj_inv=pinv)            # calibrated on the larger scene
+    assert st.graph is not None
+    for rep in range(3):
+        if rep == 1:
+            out = st.run(feat, proj, other.to(device), proj_inv=pinv)
+            _check_static_scene(out, vol, cnt, pts_other)
+            continue
+        out = st.run(feat, proj, tsdf.to(device), proj_inv=pinv)
+        _check_static_scene(out, vol, cnt, exp)
+
+
+def test_static_scene_with_no_view_left_after_the_drop(device):
+    """a slot built on a normal one-view scene, then a scene whose only view keeps one sample: nothing is left after the
+    drop, the plan's M >= 1 watch (rma.aggregate_points_static, lo = 1) flags the replay and detect()'s eager re-run raises
+    TypeError like the reference (ray_marching.py:300); the next normal scene through the same slot is served by the graph
+    and is correct"""
+    from cnrma_amd import pipeline
+    g = load_golden(QUIRK_SINGLE_VIEW)
+    feat, proj, pinv = t(g["features"], device), t(g["projection"]), t(g["proj_inv"])
+    tsdf = t(g["tsdf"])
+    normal = tsdf.flip(0).contiguous()
+    vol, cnt, pts = _oracle_scene(g, normal)
+    assert pts.shape[0] > 100
+    backbone, head = _model(feat.shape[1], device)
+    cfg = pipeline.SceneConfig(g["dims"], voxel_size=g["voxel_size"], origin=g["origin"], stride=g["stride"],
+                               n_steps=g["n_steps"], thr=g["thr"], max_points=500000, sample_seed=11)
+    st = pipeline.StaticScene(cfg, backbone, head, device)
+    st.build(feat, proj, normal.to(device), proj_inv=pinv)
+    assert st.graph is not None
+    out = st.run(feat, proj, tsdf.to(device), proj_inv=pinv)
+    with pytest.raises(_lib_error()):
+        _detections(out)                                             # the replay is flagged: M = 0 < 1
+    with pytest.raises(TypeError):
+        st.detect(feat, proj, tsdf.to(device))
+    b, s, info = st.detect(feat, proj, normal.to(device))
+    assert info["static"] is True and info["M"] == pts.shape[0]
+    out = st.run(feat, proj, normal.to(device), proj_inv=pinv)
+    _check_static_scene(out, vol, cnt, pts)
+
+
+def _lib_error():
+    from cnrma_amd import _lib
+    return _lib.CnrmaError
