@@ -301,6 +301,114 @@ def run_quirk_single_view(rm, name, sc, thr=0.05, n_steps=300):
     print(f"rma_{name}.npz: V=1 raises TypeError ({os.path.getsize(path)} bytes)")
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# edge geometry: the border of the grid runs through free space (a scene larger than the grid, cut by it), cameras stand
+# outside the grid, on a lattice plane and above a corner; axis-aligned rays with exactly-zero direction components; grazing
+# rays on the rounding tie x/vs = -0.5; odd channel counts and odd map sizes
+# --------------------------------------------------------------------------------------------------------------------
+def projection_of(R, eye, f, cx, cy):
+    """[3,4] fp32 K @ [R | -R eye] in full-resolution pixels (R: world -> camera rows right, down, forward)"""
+    R, eye = np.asarray(R, np.float64), np.asarray(eye, np.float64)
+    K = np.array([[f, 0, cx], [0, f, cy], [0, 0, 1.0]])
+    return torch.from_numpy((K @ np.concatenate([R, (-R @ eye)[:, None]], axis=1)).astype(np.float32))
+
+
+def look_at(eye, target):
+    fwd = np.asarray(target, np.float64) - np.asarray(eye, np.float64)
+    fwd /= np.linalg.norm(fwd)
+    right = np.cross(fwd, [0.0, 0.0, 1.0])
+    right /= np.linalg.norm(right)
+    return np.stack([right, np.cross(fwd, right), fwd])
+
+
+def box_tsdf(dims, boxes, specks=(), speck_value=1.0):
+    """free space (-1) everywhere but axis-aligned boxes (centre, half extents in voxels; TSDF = -signed distance / 3 voxels,
+    clamped, on a 1/64 grid) and single-voxel specks of positive TSDF"""
+    X, Y, Z = dims
+    px, py, pz = np.meshgrid(np.arange(X), np.arange(Y), np.arange(Z), indexing="ij")
+    d = np.full(dims, np.inf)
+    for c, h in boxes:
+        q = np.stack([np.abs(px - c[0]) - h[0], np.abs(py - c[1]) - h[1], np.abs(pz - c[2]) - h[2]])
+        d = np.minimum(d, np.sqrt((np.maximum(q, 0) ** 2).sum(0)) + np.minimum(q.max(0), 0))
+    tsdf = np.round(np.clip(-d / 3.0, -1.0, 1.0) * 64) / 64
+    for s in specks:
+        tsdf[s] = speck_value
+    return torch.from_numpy(tsdf.astype(np.float32)).view(1, 1, X, Y, Z)
+
+
+def edge_scene(dims, origin, stride, C, hw, projections, tsdf, seed):
+    V = len(projections)
+    g = torch.Generator().manual_seed(seed)
+    feats = torch.round(torch.randn(V, 1, C, hw[0], hw[1], generator=g) * 8) / 8          # compresses well
+    return dict(features=feats, projection=torch.stack(projections).view(V, 1, 3, 4), tsdf=tsdf, dims=tuple(dims),
+                voxel_size=0.04, origin=tuple(origin), stride=stride)
+
+
+EDGE_AXIS_DIMS, EDGE_AXIS_ORIGIN = (50, 45, 27), (-0.31, 0.173, -0.05)
+EDGE_AXIS_SPECKS = ((9, 21, 14), (30, 21, 14), (41, 21, 14), (20, 8, 20), (44, 38, 4), (5, 40, 22))
+
+
+def edge_axis_projections():
+    """view 0: outside, 0.19 m beyond the low-x face, looking along +x (exact permutation, f = 64, principal point on the
+    feature-map pixel (20, 15) at stride 4: the ray of that pixel runs along the axis, its row and column have exactly-zero
+    direction components); view 1: inside, the eye on the lattice plane of column 23 (camera depth exactly 0 there, the
+    columns below it behind the camera); view 2: above the high corner, oblique -- some rays miss the grid"""
+    ox, oy, oz = EDGE_AXIS_ORIGIN
+    R = [[0, -1, 0], [0, 0, -1], [1, 0, 0]]
+    x23 = float((torch.tensor(23.0) * 0.04 + torch.tensor(ox, dtype=torch.float32)).item())      # fl(fl(23 vs) + ox)
+    eye2 = np.array([ox + 50 * 0.04 + 0.15, oy + 45 * 0.04 + 0.2, oz + 27 * 0.04 + 0.35])
+    return [projection_of(R, (-0.5, 1.0, 0.5), 64.0, 80.0, 60.0),
+            projection_of(R, (x23, 1.0, 0.5), 64.0, 80.0, 60.0),
+            projection_of(look_at(eye2, (ox + 0.9, oy + 0.8, oz + 0.3)), eye2, 64.0, 80.0, 60.0)]
+
+
+def edge_outside_axis_scene():
+    tsdf = box_tsdf(EDGE_AXIS_DIMS, [((38, 10, 8), (5, 4, 4)), ((12, 34, 18), (4, 5, 5)), ((33, 33, 6), (3, 2, 3))],
+                    EDGE_AXIS_SPECKS)
+    return edge_scene(EDGE_AXIS_DIMS, EDGE_AXIS_ORIGIN, 4, 8, (30, 40), edge_axis_projections(), tsdf, seed=21)
+
+
+def edge_cropped_c12_scene():
+    """stride 1, C = 12, 29 x 37 maps (H*W odd); view 0 stands half a voxel below the low-x face (fl(eye_x - ox) =
+    -0.5 vs exactly) and looks along +y: the rays of pixel column 18 have dx = 0 and run in the plane x = ox - 0.5 vs, on
+    the rounding tie of voxel column 0"""
+    vs32 = np.float32(0.04)
+    eye_x = np.float32(0.0)
+    ox = np.float32(eye_x + np.float32(0.5) * vs32)
+    assert np.float32(eye_x - ox) == -np.float32(0.5) * vs32
+    origin = (float(ox), -0.1, 0.0)
+    dims = (33, 20, 41)
+    R = [[1, 0, 0], [0, 0, -1], [0, 1, 0]]
+    projs = [projection_of(R, (float(eye_x), -0.25, 0.75), 16.0, 18.0, 14.0),
+             projection_of(look_at((0.75, 0.3125, 1.0), (0.2, 0.55, 0.3)), (0.75, 0.3125, 1.0), 16.0, 18.0, 14.0)]
+    tsdf = box_tsdf(dims, [((8, 12, 10), (4, 3, 6)), ((24, 9, 30), (5, 4, 4)), ((16, 17, 2), (3, 5, 3))],
+                    ((0, 10, 20), (0, 15, 26), (20, 5, 22), (28, 14, 12)))
+    return edge_scene(dims, origin, 1, 12, (29, 37), projs, tsdf, seed=22)
+
+
+def run_edge_scenes(rm, tr):
+    run_scene(rm, tr, "edge_outside_axis", edge_outside_axis_scene())
+    check_edge_fixture("edge_outside_axis")
+    run_scene(rm, tr, "edge_cropped_c12", edge_cropped_c12_scene(), thr=0.03)
+    check_edge_fixture("edge_cropped_c12", need_depth0=False, need_tie=True)
+
+
+def check_edge_fixture(name, need_exit=True, need_entry=True, need_depth0=True, need_tie=False):
+    """the fixture holds the edges it is for (tests/test_oracle_cpu.py re-derives the same facts)"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import edge_facts, load_golden
+    f = edge_facts(load_golden(name))
+    print(f"rma_{name}.npz edges: {f}")
+    assert f["zero_dir"] > 0 and f["start_outside"] > 0, (name, f)
+    assert not need_exit or f["exit_free"] > 0, (name, f)
+    assert not need_entry or f["depth_before_entry"] > 0, (name, f)
+    assert f["depth_le0"] > 0 and (not need_depth0 or f["depth_eq0"] > 0), (name, f)
+    assert not need_tie or f["tie"] > 0, (name, f)
+    assert f["thr_margin"] > 1e-6, (name, f)              # no weight flips with the 1-ulp tail of the CPU sigmoid
+    assert f["single_views"] == 0, (name, f)              # a one-sample view is the quirk case (QUIRK_SCENES)
+    return f
+
+
 def run_decode(head_mod):
     """a12: _bbox_pred_to_bbox for the 6-DoF and the 8->7 'fcaf3d' yaw parametrisation + compute_centerness."""
     g = torch.Generator().manual_seed(3)
@@ -411,6 +519,7 @@ def main():
     P = sc["projection"]
     P[0, 0, :, :3] = -P[0, 0, :, :3]            # mirror the camera through its centre: every ray leaves the grid
     run_scene(rm, tr, "edge_empty_view", sc)
+    run_edge_scenes(rm, tr)
     run_quirk_scene(rm, "edge_single_sample", quirk_neus_scene(0))
     run_quirk_scene(rm, "edge_single_sample_v1", quirk_neus_scene(1))
     run_quirk_scene(rm, "edge_single_sample_depth", quirk_depth_scene())
@@ -431,6 +540,11 @@ if __name__ == "__main__" and "--quirks" in sys.argv:
     run_quirk_scene(_rm, "edge_single_sample_v1", quirk_neus_scene(1))
     run_quirk_scene(_rm, "edge_single_sample_depth", quirk_depth_scene())
     run_quirk_single_view(_rm, "edge_single_sample_only", quirk_neus_scene(0))
+    sys.exit(0)
+
+if __name__ == "__main__" and "--edges" in sys.argv:
+    _rm, _, _tr, _ = R.load_reference()
+    run_edge_scenes(_rm, _tr)
     sys.exit(0)
 
 if __name__ == "__main__" and "--atlas3d" in sys.argv:

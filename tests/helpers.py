@@ -5,7 +5,9 @@ import numpy as np
 import torch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SCENES = ["tiny", "tiny_boxes_origin", "mini_p", "edge_empty_view"]
+SCENES = ["tiny", "tiny_boxes_origin", "mini_p", "edge_empty_view", "edge_outside_axis", "edge_cropped_c12"]
+# scenes whose grid border runs through free space, with cameras outside / on a lattice plane and axis-aligned rays
+EDGE_SCENES = ["edge_outside_axis", "edge_cropped_c12"]
 # scenes in which a view keeps exactly one sample and the reference drops it (ray_marching.py:781-782 / :930-931 inside the
 # bare except of :277-287): their fixtures hold per-view rows only for the views the reference kept, so they are not in
 # SCENES; dedicated tests use them (make_golden.py run_quirk_scene)
@@ -73,3 +75,53 @@ def elementwise_error(got, exp):
     err = np.abs(got - exp)
     worst = np.minimum(err, err / np.maximum(np.abs(exp), 1e-300))
     return float(worst.max()) if worst.size else 0.0
+
+
+def edge_facts(g):
+    """what the edge fixtures (make_golden.py edge_outside_axis / edge_cropped_c12) are for, re-derived from their inputs with
+    the oracle (ray parameters pinned through the fixture's proj_inv): counts of rays with an exactly-zero direction
+    component, of rays that start outside the grid and enter it, of rays whose last kept NeuS sample is their last in-grid
+    sample before they leave through free space, of view-0 depth hits at the step before entry, of voxels with camera
+    depth <= 0 (== 0), of in-grid samples on the rounding tie x/vs = -0.5; the smallest distance of a NeuS weight of an
+    in-grid sample to thr, and the number of views that keep exactly one sample"""
+    from oracle import rma_oracle as O
+    dims, vs, origin, N, thr, stride = g["dims"], g["voxel_size"], g["origin"], g["n_steps"], g["thr"], g["stride"]
+    feats, tsdf = g["features"], t(g["tsdf"])
+    V, _, H, W = feats.shape
+    org = torch.tensor(origin, dtype=torch.float32).view(3, 1, 1)
+    f = dict(zero_dir=0, start_outside=0, exit_free=0, depth_before_entry=0, depth_le0=0, depth_eq0=0, tie=0,
+             thr_margin=float("inf"), single_views=0)
+    idx = O.voxel_coordinates(dims)
+    world = torch.cat((idx.float() * vs + org.view(3, 1), torch.ones(1, idx.shape[1])), dim=0)
+    for v in range(V):
+        ps = O.scale_projection(t(g["projection"][v]), stride)
+        cz = O.matmul_fma_chain(ps, world)[2]
+        f["depth_le0"] += int((cz <= 0).sum())
+        f["depth_eq0"] += int((cz == 0).sum())
+        o, d = O.ray_params(ps, H, W, t(g["proj_inv"][v]))
+        f["zero_dir"] += int((d == 0).any(dim=0).sum())
+        place, _, valid, sdf = O.march_samples(o, d, tsdf, dims, vs, origin, N)
+        f["start_outside"] += int((~valid[:, 0] & valid.any(dim=1)).sum())
+        f["tie"] += int((((place - org) / vs == -0.5).any(dim=0) & valid).sum())
+        # NeuS weights before the threshold (neus_weights, :757-763)
+        s = torch.sigmoid(-sdf)
+        alpha = torch.clamp((s - torch.cat((s[:, 1:], s[:, -1:]), dim=1)) / s, min=0)
+        T_next = torch.cumprod(1 - alpha, dim=1)
+        w = torch.cat((torch.ones_like(T_next[:, :1]), T_next[:, :-1]), dim=1) * alpha
+        f["thr_margin"] = min(f["thr_margin"], float((w[valid].double() - thr).abs().min()))
+        keep = valid & (w >= thr)
+        f["single_views"] += int(keep.sum()) == 1
+        steps = torch.arange(N).expand_as(keep)
+        last = torch.where(keep, steps, -1).max(dim=1).values                      # last kept step per ray (-1: none)
+        last_valid = torch.where(valid, steps, -1).max(dim=1).values               # last in-grid step per ray
+        ray = torch.nonzero(last >= 0)[:, 0]
+        n = last[ray]
+        f["exit_free"] += int(((n == last_valid[ray]) & (n + 1 < N) & (sdf[ray, n] < 0)).sum())
+        if v == 0:                                                                  # depth rows are stored for view 0
+            prod = torch.cat((sdf[:, :-1] * sdf[:, 1:], torch.ones(sdf.shape[0], 1)), dim=1)
+            change = prod <= 0
+            best = torch.argmax(change.float(), dim=1)
+            hit = change.any(dim=1) & (best + 1 < N)
+            r = torch.nonzero(hit)[:, 0]
+            f["depth_before_entry"] += int((~valid[r, best[r]] & valid[r, best[r] + 1]).sum())
+    return f

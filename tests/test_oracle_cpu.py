@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 import torch
 
-from helpers import QUIRK_SCENES, QUIRK_SINGLE_VIEW, SCENES, bits_equal, count_mismatch, load_golden, t
+from helpers import EDGE_SCENES, QUIRK_SCENES, QUIRK_SINGLE_VIEW, SCENES, bits_equal, count_mismatch, edge_facts, load_golden, t
 from oracle import rma_oracle as O
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -153,6 +153,22 @@ def test_quirk_fixtures_hold_the_cases_they_are_for():
     assert list(d["depth_k0_skipped"]) == [True, False, False] and min(d["depth_k0_counts"][1:]) >= 50
     for g in (a, b, d):
         assert not g["depth_k1_skipped"].any() and not g["depth_k2_skipped"].any()
+
+
+@pytest.mark.parametrize("name", EDGE_SCENES)
+def test_edge_fixtures_hold_the_edges_they_are_for(name):
+    """the edge fixtures keep testing what they claim (the facts make_golden.py asserts, re-derived with the oracle): rays
+    with exactly-zero direction components, rays that start outside the grid, rays whose last kept NeuS sample is their last
+    in-grid sample before they leave through free space, view-0 depth hits at the step before entry, voxels behind or on the
+    plane of a camera, samples on the rounding tie x/vs = -0.5; no NeuS weight within 1e-6 of thr and no one-sample view"""
+    f = edge_facts(load_golden(name))
+    assert f["zero_dir"] > 0 and f["start_outside"] > 0 and f["exit_free"] > 0 and f["depth_before_entry"] > 0, f
+    assert f["depth_le0"] > 0, f
+    assert f["thr_margin"] > 1e-6 and f["single_views"] == 0, f
+    if name == "edge_outside_axis":
+        assert f["depth_eq0"] > 0, f                       # view 1 stands on the lattice plane of column 23
+    else:
+        assert f["tie"] > 0, f                             # view 0's grazing rays run in the plane x = ox - 0.5 vs
 
 
 def test_single_view_of_one_sample_raises_like_reference():
