@@ -374,29 +374,29 @@ __device__ __forceinline__ float apply_act(float v, int act) {
 // a compact 4x4x4-voxel block whenever the parents are compact: what the gather-once convolution needs.
 __device__ __forceinline__ int morton_child(int z) { return ((z & 1) << 2) | (z & 2) | ((z >> 2) & 1); }
 
-struct ConvArgs {
-  const float* in; int Cin;
-  const int32_t* nbr; int K;
-  const float* weight; int Cout;
-  const float* scale; const float* shift; const float* residual; int act;
-  float* out; int64_t no_cap; const int32_t* no_dev;
-  int slices;        // > 1: generative transpose, slice z uses W[z] and writes row slices * i + morton_child(z)
-  int splits;        // > 1: split over kernel offsets, raw partial sums go to slab[z]
-  int k_per_split;
-  float* slab;       // [splits][no_cap][Cout]
+struct ConvArgs {                 // (every field defaults to zero / null: launchers name only what they set)
+  const float* in = nullptr; int Cin = 0;
+  const int32_t* nbr = nullptr; int K = 0;
+  const float* weight = nullptr; int Cout = 0;
+  const float* scale = nullptr; const float* shift = nullptr; const float* residual = nullptr; int act = 0;
+  float* out = nullptr; int64_t no_cap = 0; const int32_t* no_dev = nullptr;
+  int slices = 0;    // > 1: generative transpose, slice z uses W[z] and writes row slices * i + morton_child(z)
+  int splits = 0;    // > 1: split over kernel offsets, raw partial sums go to slab[z]
+  int k_per_split = 0;
+  float* slab = nullptr;       // [splits][no_cap][Cout]
   // pre-split bf16 companions of the features: [rows + 1][C/8][3 planes][8] (hi/mid/lo of 8 channels = 48 B), the
   // extra last row is all zeros and stands in for missing neighbours (no select in the gather)
-  const uint16_t* in_split; int64_t in_zero_row;
-  uint16_t* out_split; int64_t out_zero_row;
+  const uint16_t* in_split = nullptr; int64_t in_zero_row = 0;
+  uint16_t* out_split = nullptr; int64_t out_zero_row = 0;
   // f16x3: upper bounds of |features| / |weights| (device scalars) that fix the power-of-two operand scales, and the
   // running maximum of |outputs| for the consumers of this layer (atomicMax on the bit pattern; pre-zeroed by the host)
-  const float* in_amax; const float* w_amax; float* out_amax;
+  const float* in_amax = nullptr; const float* w_amax = nullptr; float* out_amax = nullptr;
   // pair-list mode (cnrma_sparse_conv_pairs_f16x3): the rows are (output, input) pairs grouped by kernel offset in runs
   // padded to 128 rows; tile_tap[row / 128] = the offset whose weights the run uses, w_taps = offsets in the image
-  const int32_t* tile_tap; int w_taps;
-  int xcd_tiles;     // > 0: number of row tiles; block b works on tile (b % 8) * ceil(tiles / 8) + b / 8 -- workgroups are dealt round-
+  const int32_t* tile_tap = nullptr; int w_taps = 0;
+  int xcd_tiles = 0; // > 0: number of row tiles; block b works on tile (b % 8) * ceil(tiles / 8) + b / 8 -- workgroups are dealt round-
                      // robin over the 8 XCDs, so each XCD (private L2) then owns one contiguous eighth of the rows
-  int ablate;        // diagnostic kernels only (ABL = true; cnrma_debug_conv_tuning): bit 0 no MFMAs, 1 no A loads, 2 no B loads,
+  int ablate = 0;    // diagnostic kernels only (ABL = true; cnrma_debug_conv_tuning): bit 0 no MFMAs, 1 no A loads, 2 no B loads,
                      // 3 no LDS stores, 4 no barriers -- after the first stage; results are then meaningless, only the time counts
 };
 
@@ -1419,18 +1419,49 @@ static constexpr ConvTune k_conv_tune{};
 #define CNRMA_CONV_TUNE k_conv_tune
 #endif
 
+// the MODE template argument of sparse_conv_bf16x6_kernel.  CONV_EXACT: bf16x6 on a split weight image, or the fp32 MFMA kernel
+// when the launch has no image
+enum ConvMode { CONV_EXACT = 0, CONV_F16X3 = 1, CONV_BF16 = 2 };
+
+// grid of a grid-stride loop over `threads` work items in 256-thread blocks, at most `cap` blocks
+static int64_t capped_blocks(int64_t threads, int64_t cap) {
+  const int64_t b = ceil_div(threads, 256);
+  return b > cap ? cap : b;
+}
+
+// the fields every convolution launch names; the others keep their zero defaults until the call site sets them
+static ConvArgs conv_args(const float* in, int Cin, const int32_t* nbr, int K, int Cout, float* out, int64_t no_cap,
+                          const int32_t* no_dev, void* slab = nullptr) {
+  ConvArgs p;
+  p.in = in; p.Cin = Cin; p.nbr = nbr; p.K = K; p.Cout = Cout; p.out = out; p.no_cap = no_cap; p.no_dev = no_dev;
+  p.slices = 1; p.splits = 1; p.k_per_split = K; p.slab = reinterpret_cast<float*>(slab);
+  return p;
+}
+
+// the fused epilogue: out = act(sum * scale + shift + residual)
+static ConvArgs& with_epilogue(ConvArgs& p, const float* scale, const float* shift, const float* residual, int act) {
+  p.scale = scale; p.shift = shift; p.residual = residual; p.act = act;
+  return p;
+}
+
+// a launch split p.splits ways left raw partial sums in p.slab: conv_reduce_kernel adds them in slab order + the epilogue
+static void reduce_splits(const ConvArgs& p, hipStream_t st) {
+  if (p.splits > 1)
+    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)capped_blocks(p.no_cap * p.Cout / 4 + 1, 4096)), dim3(256), 0, st, p);
+}
+
 enum ConvShape { T128x128, T128x64, T64x64, T128x32, T64x128, T256x128, T256x64, N_CONV_SHAPES };   // the last two: warp-specialised kernel only
 struct ConvPlan { int shape, bm, bn, splits, k_per_split, pf; };
 
 // tile shape, split count over the kernel offsets and prefetch depth of one launch: a pure function of the layer's
 // sizes (the CAPACITY of the output, not its live row count), so a captured launch sequence replays the same kernels
-ConvPlan plan_conv(int64_t no_cap, int Cin, int Cout, int K, int mode, bool six, int slices, bool has_ws, size_t ws_bytes) {
+ConvPlan plan_conv(int64_t no_cap, int Cin, int Cout, int K, ConvMode mode, bool six, int slices, bool has_ws, size_t ws_bytes) {
   static const int bms[] = {128, 128, 64, 128, 64, 256, 256}, bns[] = {128, 64, 64, 32, 128, 128, 64};
   // tile choice, measured per layer class and precision on MI355X at the ScanNet shape: f16x3 tiles
   // need fewer registers and less LDS (4-7 blocks per CU), which moves the optimum to 64-row tiles almost everywhere
   int sh;
   if (Cout <= 32) sh = T128x32;
-  else if (six && mode >= 1) {
+  else if (six && mode != CONV_EXACT) {
     if (Cout >= 128) sh = no_cap >= 16384 && no_cap < 40000 ? T128x128 : (no_cap < 1000 && Cout < 256 ? T64x64 : T64x128);
     else sh = no_cap >= 200000 && Cin > 32 ? T128x64 : T64x64;
   }
@@ -1441,7 +1472,7 @@ ConvPlan plan_conv(int64_t no_cap, int Cin, int Cout, int K, int mode, bool six,
   else if (six && Cin <= 32) sh = T64x64;
   else sh = T128x64;
   const ConvTune t = CNRMA_CONV_TUNE;
-  if (t.shape >= 0 && t.shape < N_CONV_SHAPES && (six || t.shape < T64x128) && (t.shape < T256x128 || (six && mode == 1 && t.ws >= 2)))
+  if (t.shape >= 0 && t.shape < N_CONV_SHAPES && (six || t.shape < T64x128) && (t.shape < T256x128 || (six && mode == CONV_F16X3 && t.ws >= 2)))
     sh = t.shape;
   ConvPlan pl{sh, bms[sh], bns[sh], 1, K, 1};
   if (slices == 1 && has_ws) {
@@ -1457,33 +1488,29 @@ ConvPlan plan_conv(int64_t no_cap, int Cin, int Cout, int K, int mode, bool six,
   }
   // two stages of loads in flight where a block is a chain of latency-bound stages: short f16x3 layers (Cin >= 64: the
   // neighbour indices must be two stages ahead of their gathers)
-  const bool pf2_ok = six && mode == 1 && Cin >= 2 * BK && sh != T128x32 && sh != T128x128 && sh < T256x128;    // 128x128 would spill
+  const bool pf2_ok = six && mode == CONV_F16X3 && Cin >= 2 * BK && sh != T128x32 && sh != T128x128 && sh < T256x128;    // 128x128 would spill
   if (pf2_ok && K > 1) pl.pf = no_cap < CONV_PF2_ROWS ? 2 : 1;
   if (t.pf > 0 && pf2_ok) pl.pf = t.pf >= 2 ? 2 : 1;
   return pl;
 }
 
-int launch_conv(const float* in, int Cin, const int32_t* nbr, int K, const float* weight, int Cout, const float* scale,
-                const float* shift, const float* residual, int act, float* out, int64_t no_cap, const int32_t* no_dev,
-                int slices, void* workspace, size_t ws_bytes, hipStream_t st, const void* weight_split = nullptr,
-                const void* in_split = nullptr, int64_t in_zero_row = 0, void* out_split = nullptr,
-                int64_t out_zero_row = 0, int mode = 0, const float* in_amax = nullptr, float* out_amax = nullptr,
-                const int32_t* tile_tap = nullptr, int w_taps = 0) {
+// the stage kernel: p carries the layer (p.slab = the split workspace or null, p.slices = 8 for a generative transpose); `image`
+// is the prepared weight image of `mode` (null: the fp32 kernel on p.weight)
+int launch_conv(ConvArgs p, ConvMode mode, const void* image, size_t ws_bytes, hipStream_t st) {
+  const int Cin = p.Cin, Cout = p.Cout, K = p.K, slices = p.slices;
+  const int64_t no_cap = p.no_cap;
   if (Cin <= 0 || Cout <= 0 || K <= 0 || K > 27 || no_cap <= 0) return CNRMA_EINVAL;
-  if (out_split != nullptr && (Cout % 8 != 0 || weight_split == nullptr)) return CNRMA_EINVAL;
-  if (in_split != nullptr && (Cin % 32 != 0 || weight_split == nullptr)) return CNRMA_EINVAL;
-  ConvArgs p{in, Cin, nbr, K, weight, Cout, scale, shift, residual, act, out, no_cap, no_dev, slices, 1, K,
-             reinterpret_cast<float*>(workspace), reinterpret_cast<const uint16_t*>(in_split), in_zero_row,
-             reinterpret_cast<uint16_t*>(out_split), out_zero_row, in_amax, nullptr, out_amax, tile_tap, w_taps};
-  if (mode == 2 && (weight_split == nullptr || in_split != nullptr || out_split != nullptr)) return CNRMA_EINVAL;
-  if (mode == 1) {
-    if (weight_split == nullptr || in_amax == nullptr || in_split != nullptr || out_split != nullptr) return CNRMA_EINVAL;
-    p.w_amax = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(weight_split) +
-                                              2 * (int64_t)(slices > 1 ? slices : 1) * (tile_tap ? w_taps : K) * Cin *
+  if (p.out_split != nullptr && (Cout % 8 != 0 || image == nullptr)) return CNRMA_EINVAL;
+  if (p.in_split != nullptr && (Cin % 32 != 0 || image == nullptr)) return CNRMA_EINVAL;
+  if (mode == CONV_BF16 && (image == nullptr || p.in_split != nullptr || p.out_split != nullptr)) return CNRMA_EINVAL;
+  if (mode == CONV_F16X3) {
+    if (image == nullptr || p.in_amax == nullptr || p.in_split != nullptr || p.out_split != nullptr) return CNRMA_EINVAL;
+    p.w_amax = reinterpret_cast<const float*>(reinterpret_cast<const uint16_t*>(image) +
+                                              2 * (int64_t)(slices > 1 ? slices : 1) * (p.tile_tap ? p.w_taps : K) * Cin *
                                                   conv_cout_padded(Cout));
   }
-  const bool six = weight_split != nullptr && Cin % 32 == 0;
-  const ConvPlan pl = plan_conv(no_cap, Cin, Cout, K, mode, six, slices, workspace != nullptr, ws_bytes);
+  const bool six = image != nullptr && Cin % 32 == 0;
+  const ConvPlan pl = plan_conv(no_cap, Cin, Cout, K, mode, six, slices, p.slab != nullptr, ws_bytes);
   const int shape = pl.shape, bm = pl.bm, bn = pl.bn;
   p.ablate = CNRMA_CONV_TUNE.ablate;
   p.splits = pl.splits;
@@ -1491,47 +1518,48 @@ int launch_conv(const float* in, int Cin, const int32_t* nbr, int K, const float
   dim3 grid((unsigned)ceil_div(no_cap, bm), (unsigned)ceil_div(Cout, bn), (unsigned)(slices > 1 ? slices : p.splits));
   // XCD-aware tile order (stage kernel on prepared weights; the pair-list runs keep their tile_tap order)
   const int xcd = CNRMA_CONV_TUNE.xcd >= 0 ? CNRMA_CONV_TUNE.xcd : CONV_XCD_ORDER;
-  if (xcd && weight_split != nullptr && Cin % 32 == 0 && tile_tap == nullptr && grid.x >= 64) {
+  if (xcd && six && p.tile_tap == nullptr && grid.x >= 64) {
     p.xcd_tiles = (int)grid.x;
     grid.x = (grid.x + 7u) / 8u * 8u;
   }
   const bool fast = (Cin % 32 == 0) && (Cout % 4 == 0);
-  const bool has_res = residual != nullptr && p.splits == 1;   // split layers add the residual in the reduce kernel
-  if (weight_split != nullptr && Cin % 32 == 0) {
-    const __bf16* wt = reinterpret_cast<const __bf16*>(weight_split);
+  const bool has_res = p.residual != nullptr && p.splits == 1;   // split layers add the residual in the reduce kernel
+  const bool in_split = p.in_split != nullptr;
+  if (six) {
+    const __bf16* wt = reinterpret_cast<const __bf16*>(image);
 #ifdef CNRMA_EXPERIMENTS            // the diagnostic (ablation) instantiation of the stage kernel
 #define CNRMA_CONV6_ABL(WM, WN, TM_, TN_)                                                                          \
-    else if (mode == 1 && !has_res && CNRMA_CONV_TUNE.ablate != 0)                                                 \
+    else if (mode == CONV_F16X3 && !has_res && CNRMA_CONV_TUNE.ablate != 0)                                        \
       hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, false, 1, 1, true>), grid, dim3(256), 0, st, p, wt);
 #else
 #define CNRMA_CONV6_ABL(WM, WN, TM_, TN_)
 #endif
 #define CNRMA_CONV6_LAUNCH(WM, WN, TM_, TN_)                                                                       \
   do {                                                                                                             \
-    if (mode == 2 && has_res)                                                                                      \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 2>), grid, dim3(256), 0, st, p, wt);  \
-    else if (mode == 2)                                                                                            \
+    if (mode == CONV_BF16 && has_res)                                                                              \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 2>), grid, dim3(256), 0, st, p, wt); \
+    else if (mode == CONV_BF16)                                                                                    \
       hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, false, 2>), grid, dim3(256), 0, st, p, wt); \
     CNRMA_CONV6_ABL(WM, WN, TM_, TN_)                                                                              \
-    else if (mode == 1 && has_res && pl.pf == 2)                                                                   \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 1, (TM_ * TN_ <= 2 ? 2 : 1)>), grid, dim3(256), 0, st, p, wt);  \
-    else if (mode == 1 && pl.pf == 2)                                                                              \
+    else if (mode == CONV_F16X3 && has_res && pl.pf == 2)                                                          \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 1, (TM_ * TN_ <= 2 ? 2 : 1)>), grid, dim3(256), 0, st, p, wt); \
+    else if (mode == CONV_F16X3 && pl.pf == 2)                                                                     \
       hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, false, 1, (TM_ * TN_ <= 2 ? 2 : 1)>), grid, dim3(256), 0, st, p, wt); \
-    else if (mode == 1 && has_res)                                                                                      \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 1>), grid, dim3(256), 0, st, p, wt);  \
-    else if (mode == 1)                                                                                            \
+    else if (mode == CONV_F16X3 && has_res)                                                                        \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 1>), grid, dim3(256), 0, st, p, wt); \
+    else if (mode == CONV_F16X3)                                                                                   \
       hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, false, 1>), grid, dim3(256), 0, st, p, wt); \
     else if (has_res && in_split)                                                                                  \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, true, 0>), grid, dim3(256), 0, st, p, wt);   \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, true, 0>), grid, dim3(256), 0, st, p, wt); \
     else if (has_res)                                                                                              \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 0>), grid, dim3(256), 0, st, p, wt);  \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, true, false, 0>), grid, dim3(256), 0, st, p, wt); \
     else if (in_split)                                                                                             \
-      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, true, 0>), grid, dim3(256), 0, st, p, wt);  \
+      hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, true, 0>), grid, dim3(256), 0, st, p, wt); \
     else                                                                                                           \
       hipLaunchKernelGGL((sparse_conv_bf16x6_kernel<WM, WN, TM_, TN_, false, false, 0>), grid, dim3(256), 0, st, p, wt); \
   } while (0)
 #ifdef CNRMA_EXPERIMENTS
-    const int ws_slots = mode == 1 && in_split == nullptr && shape != T128x32 ? (CNRMA_CONV_TUNE.ws >= 0 ? CNRMA_CONV_TUNE.ws : CONV_WS_SLOTS) : 0;
+    const int ws_slots = mode == CONV_F16X3 && !in_split && shape != T128x32 ? (CNRMA_CONV_TUNE.ws >= 0 ? CNRMA_CONV_TUNE.ws : CONV_WS_SLOTS) : 0;
     if (ws_slots >= 2 && CNRMA_CONV_TUNE.ablate == 0) {
       // warp-specialised kernel: 8 waves, dynamic LDS = ring + counters (above 64 KB the limit is raised per kernel)
       const int rc = launch_conv_ws(shape, ws_slots, has_res, grid, p, wt, st);
@@ -1548,11 +1576,7 @@ int launch_conv(const float* in, int Cin, const int32_t* nbr, int K, const float
     }
 #undef CNRMA_CONV6_LAUNCH
 #undef CNRMA_CONV6_ABL
-    if (p.splits > 1) {
-      int64_t blocks = ceil_div(no_cap * Cout / 4 + 1, 256);
-      if (blocks > 4096) blocks = 4096;
-      hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-    }
+    reduce_splits(p, st);
     CNRMA_LAUNCH_CHECK();
     return 0;
   }
@@ -1575,11 +1599,7 @@ int launch_conv(const float* in, int Cin, const int32_t* nbr, int K, const float
     default: return CNRMA_EINVAL;
   }
 #undef CNRMA_CONV_LAUNCH
-  if (p.splits > 1) {
-    int64_t blocks = ceil_div(no_cap * Cout / 4 + 1, 256);
-    if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, p);
-  }
+  reduce_splits(p, st);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
@@ -3843,8 +3863,8 @@ extern "C" int cnrma_sparse_conv_plan(int64_t no_cap, int Cin, int Cout, int K, 
   // shape id}; mode 0 fp32 / bf16x6 weights absent = fp32 MFMA kernel, 1 = f16x3, 2 = bf16, 3 = bf16x6
   if (out6 == nullptr || Cin <= 0 || Cout <= 0 || K <= 0 || K > 27 || no_cap <= 0 || mode < 0 || mode > 3) return CNRMA_EINVAL;
   const bool six = mode != 0 && Cin % 32 == 0;
-  const ConvPlan pl = plan_conv(no_cap, Cin, Cout, K, mode == 3 ? 0 : mode, six, slices > 1 ? slices : 1, workspace_bytes > 0,
-                                workspace_bytes);
+  const ConvMode m = mode == 3 ? CONV_EXACT : static_cast<ConvMode>(mode);
+  const ConvPlan pl = plan_conv(no_cap, Cin, Cout, K, m, six, slices > 1 ? slices : 1, workspace_bytes > 0, workspace_bytes);
   out6[0] = pl.bm; out6[1] = pl.bn; out6[2] = pl.splits; out6[3] = pl.k_per_split; out6[4] = pl.pf; out6[5] = pl.shape;
   return 0;
 }
@@ -3853,16 +3873,16 @@ extern "C" int cnrma_sparse_conv_f32(const float* in_feats, int Cin, const int32
                                      int Cout, const float* scale, const float* shift, const float* residual, int act,
                                      float* out_feats, int64_t no_cap, const int32_t* no_dev, void* workspace,
                                      size_t workspace_bytes, void* stream) {
-  return launch_conv(in_feats, Cin, nbr, K, weight, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1,
-                     workspace, workspace_bytes, as_stream(stream));
+  ConvArgs p = conv_args(in_feats, Cin, nbr, K, Cout, out_feats, no_cap, no_dev, workspace);
+  p.weight = weight;
+  return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_EXACT, nullptr, workspace_bytes, as_stream(stream));
 }
 
 extern "C" int cnrma_sparse_conv_prepare_weights(const float* weight, int K, int Cin, int Cout, void* weight_split,
                                                  void* stream) {
   if (K <= 0 || Cin <= 0 || Cout <= 0) return CNRMA_EINVAL;
   int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  int64_t blocks = ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
+  int64_t blocks = capped_blocks(total, 4096);
   hipLaunchKernelGGL(prep_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<__bf16*>(weight_split), K, Cin, Cout);
   CNRMA_LAUNCH_CHECK();
@@ -3875,9 +3895,10 @@ extern "C" int cnrma_sparse_conv_bf16x6(const float* in_feats, const void* in_sp
                                         float* out_feats, void* out_split, int64_t no_cap, const int32_t* no_dev,
                                         void* workspace, size_t workspace_bytes, void* stream) {
   if (weight_split == nullptr || Cin % 32 != 0 || (in_feats == nullptr && in_split == nullptr)) return CNRMA_EINVAL;
-  return launch_conv(in_feats, Cin, nbr, K, nullptr, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1,
-                     workspace, workspace_bytes, as_stream(stream), weight_split, in_split, in_zero_row, out_split,
-                     no_cap);
+  ConvArgs p = conv_args(in_feats, Cin, nbr, K, Cout, out_feats, no_cap, no_dev, workspace);
+  p.in_split = reinterpret_cast<const uint16_t*>(in_split); p.in_zero_row = in_zero_row;
+  p.out_split = reinterpret_cast<uint16_t*>(out_split); p.out_zero_row = no_cap;
+  return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_EXACT, weight_split, workspace_bytes, as_stream(stream));
 }
 
 extern "C" int cnrma_rma_emit_features_f32(const float* feat_nhwc, const float* const* feat_nhwc_ref, int C, const void* records,
@@ -3907,8 +3928,7 @@ extern "C" int cnrma_absmax_f32(const float* in, int64_t n_cap, const int32_t* n
   hipStream_t st = as_stream(stream);
   hipError_t e = cnrma_fill_bytes(out_amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
   if (e != hipSuccess) return -(int)e;
-  int64_t blocks = ceil_div(n_cap * C / 4 + 1, 256);
-  if (blocks > 2048) blocks = 2048;
+  int64_t blocks = capped_blocks(n_cap * C / 4 + 1, 2048);
   hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, in, n_cap, n_dev, C, out_amax);
   CNRMA_LAUNCH_CHECK();
   return 0;
@@ -3934,11 +3954,9 @@ extern "C" int cnrma_sparse_conv_prepare_weights_f16(const float* weight, int K,
   float* amax = reinterpret_cast<float*>(wt + 2 * total) + 16;       // slot scratch behind the 64-byte trailer
   hipError_t e = cnrma_fill_bytes(amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
   if (e != hipSuccess) return -(int)e;
-  int64_t blocks = ceil_div(total_src / 4 + 1, 256);
-  if (blocks > 2048) blocks = 2048;
+  int64_t blocks = capped_blocks(total_src / 4 + 1, 2048);
   hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, total_src, nullptr, 1, amax);
-  blocks = ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
+  blocks = capped_blocks(total, 4096);
   hipLaunchKernelGGL(prep_weights_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, wt, K, Cin, Cout, amax);
   CNRMA_LAUNCH_CHECK();
   return 0;
@@ -4093,12 +4111,56 @@ __global__ __launch_bounds__(256) void pairs_reduce_kernel(ConvArgs p, const int
   }
 }
 
-static size_t pairs_align(size_t b) { return (b + 255) & ~(size_t)255; }
+static size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 extern "C" size_t cnrma_sparse_conv_pairs_workspace_bytes(int64_t no_cap, int K, int Cout, int64_t pair_cap) {
   if (no_cap <= 0 || K <= 0 || Cout <= 0 || pair_cap <= 0) return 0;
-  return pairs_align(PAIR_HDR * 4) + pairs_align((size_t)(pair_cap / 128 + 1) * 4) + pairs_align((size_t)pair_cap * 4) +
-         pairs_align((size_t)no_cap * K * 4) + pairs_align((size_t)pair_cap * Cout * 4);
+  return align256(PAIR_HDR * 4) + align256((size_t)(pair_cap / 128 + 1) * 4) + align256((size_t)pair_cap * 4) +
+         align256((size_t)no_cap * K * 4) + align256((size_t)pair_cap * Cout * 4);
+}
+
+// both pair-list entry points: the table regrouped into runs per kernel offset (count, plan, fill), the stage kernel over the
+// runs -- f16x3 on `image`, else fp32 on `weight` -- into one product row per pair, and the per-output sums with the epilogue `epi`
+static int launch_pairs(const float* in_feats, const float* in_amax, int Cin, const int32_t* nbr, const float* weight,
+                        const void* image, const ConvArgs& epi, int64_t pair_cap, void* workspace, size_t workspace_bytes,
+                        hipStream_t st) {
+  const int K = epi.K, Cout = epi.Cout;
+  const int64_t no_cap = epi.no_cap;
+  if (workspace == nullptr || workspace_bytes < cnrma_sparse_conv_pairs_workspace_bytes(no_cap, K, Cout, pair_cap))
+    return CNRMA_EINVAL;
+  char* w = reinterpret_cast<char*>(workspace);
+  int32_t* hdr = reinterpret_cast<int32_t*>(w);        w += align256(PAIR_HDR * 4);
+  int32_t* tile_tap = reinterpret_cast<int32_t*>(w);   w += align256((size_t)(pair_cap / 128 + 1) * 4);
+  int32_t* pair_src = reinterpret_cast<int32_t*>(w);   w += align256((size_t)pair_cap * 4);
+  int32_t* pos = reinterpret_cast<int32_t*>(w);        w += align256((size_t)no_cap * K * 4);
+  float* prod = reinterpret_cast<float*>(w);
+  const hipError_t fe = cnrma_fill_bytes(hdr, 0, PAIR_HDR * 4, st);
+  if (fe != hipSuccess) return -(int)fe;
+  if (no_cap * K >= 0x7fffffffLL) return CNRMA_EINVAL;
+  const int64_t blocks = ceil_div(no_cap * K, 256 * PAIR_EPT);
+  hipLaunchKernelGGL(pairs_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, epi.no_dev, K, hdr);
+  hipLaunchKernelGGL(pairs_plan_kernel, dim3(1), dim3(256), 0, st, K, hdr, tile_tap, pair_src, pair_cap);
+  hipLaunchKernelGGL(pairs_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, epi.no_dev, K, hdr, pair_src, pos,
+                     pair_cap);
+  CNRMA_LAUNCH_CHECK();
+  // the runs as a K = 1 layer of pair_cap rows; hdr[64 + 33] holds the live pair count
+  ConvArgs p = conv_args(in_feats, Cin, pair_src, 1, Cout, prod, pair_cap, hdr + 64 + 33);
+  p.weight = weight; p.in_amax = in_amax; p.tile_tap = tile_tap; p.w_taps = K;
+  const int rc = launch_conv(p, image != nullptr ? CONV_F16X3 : CONV_EXACT, image, 0, st);
+  if (rc != 0) return rc;
+  const unsigned rb = (unsigned)capped_blocks(no_cap * (Cout / 4), 16384);
+  if (K == 27) hipLaunchKernelGGL(pairs_reduce_kernel<27>, dim3(rb), dim3(256), 0, st, epi, pos, prod);
+  else hipLaunchKernelGGL(pairs_reduce_kernel<0>, dim3(rb), dim3(256), 0, st, epi, pos, prod);
+  CNRMA_LAUNCH_CHECK();
+  return 0;
+}
+
+// the epilogue side of a pair-list launch (the reduce kernel reads nothing else)
+static ConvArgs pairs_epilogue(int K, int Cout, const float* scale, const float* shift, const float* residual, int act, float* out,
+                               float* out_amax, int64_t no_cap, const int32_t* no_dev) {
+  ConvArgs p;
+  p.K = K; p.Cout = Cout; p.out = out; p.no_cap = no_cap; p.no_dev = no_dev; p.out_amax = out_amax;
+  return with_epilogue(p, scale, shift, residual, act);
 }
 
 extern "C" int cnrma_sparse_conv_pairs_f16x3(const float* in_feats, const float* in_amax, int Cin, const int32_t* nbr, int K,
@@ -4109,36 +4171,9 @@ extern "C" int cnrma_sparse_conv_pairs_f16x3(const float* in_feats, const float*
   if (weight_split == nullptr || Cin % 32 != 0 || Cout % 4 != 0 || in_feats == nullptr || in_amax == nullptr || nbr == nullptr ||
       K <= 1 || K > 27 || no_cap <= 0 || pair_cap <= 0 || pair_cap % 128 != 0 || pair_cap > 0x7fffff00LL)
     return CNRMA_EINVAL;
-  if (workspace == nullptr || workspace_bytes < cnrma_sparse_conv_pairs_workspace_bytes(no_cap, K, Cout, pair_cap))
-    return CNRMA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  char* w = reinterpret_cast<char*>(workspace);
-  int32_t* hdr = reinterpret_cast<int32_t*>(w);        w += pairs_align(PAIR_HDR * 4);
-  int32_t* tile_tap = reinterpret_cast<int32_t*>(w);   w += pairs_align((size_t)(pair_cap / 128 + 1) * 4);
-  int32_t* pair_src = reinterpret_cast<int32_t*>(w);   w += pairs_align((size_t)pair_cap * 4);
-  int32_t* pos = reinterpret_cast<int32_t*>(w);        w += pairs_align((size_t)no_cap * K * 4);
-  float* prod = reinterpret_cast<float*>(w);
-  const hipError_t fe = cnrma_fill_bytes(hdr, 0, PAIR_HDR * 4, st);
-  if (fe != hipSuccess) return -(int)fe;
-  if (no_cap * K >= 0x7fffffffLL) return CNRMA_EINVAL;
-  const int64_t blocks = ceil_div(no_cap * K, 256 * PAIR_EPT);
-  hipLaunchKernelGGL(pairs_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, no_dev, K, hdr);
-  hipLaunchKernelGGL(pairs_plan_kernel, dim3(1), dim3(256), 0, st, K, hdr, tile_tap, pair_src, pair_cap);
-  hipLaunchKernelGGL(pairs_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, no_dev, K, hdr, pair_src, pos,
-                     pair_cap);
-  CNRMA_LAUNCH_CHECK();
-  const int rc = launch_conv(in_feats, Cin, pair_src, 1, nullptr, Cout, nullptr, nullptr, nullptr, 0, prod, pair_cap, hdr + 64 + 33,
-                             1, nullptr, 0, st, weight_split, nullptr, 0, nullptr, 0, 1, in_amax, nullptr, tile_tap, K);
-  if (rc != 0) return rc;
-  ConvArgs p{};
-  p.K = K; p.Cout = Cout; p.scale = scale; p.shift = shift; p.residual = residual; p.act = act; p.out = out_feats;
-  p.no_cap = no_cap; p.no_dev = no_dev; p.out_amax = out_amax;
-  int64_t rb = ceil_div(no_cap * (Cout / 4), 256);
-  if (rb > 16384) rb = 16384;
-  if (K == 27) hipLaunchKernelGGL(pairs_reduce_kernel<27>, dim3((unsigned)rb), dim3(256), 0, st, p, pos, prod);
-  else hipLaunchKernelGGL(pairs_reduce_kernel<0>, dim3((unsigned)rb), dim3(256), 0, st, p, pos, prod);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
+  return launch_pairs(in_feats, in_amax, Cin, nbr, nullptr, weight_split,
+                      pairs_epilogue(K, Cout, scale, shift, residual, act, out_feats, out_amax, no_cap, no_dev), pair_cap, workspace,
+                      workspace_bytes, as_stream(stream));
 }
 
 // the same regrouping in exact fp32: the fp32 MFMA stage kernel over the pair runs (the north-star stem at CONV_PRECISION = "f32"
@@ -4150,42 +4185,14 @@ extern "C" int cnrma_sparse_conv_pairs_f32(const float* in_feats, int Cin, const
   if (weight == nullptr || Cin % 32 != 0 || Cout % 4 != 0 || in_feats == nullptr || nbr == nullptr || K <= 1 || K > 27 || no_cap <= 0 ||
       pair_cap <= 0 || pair_cap % 128 != 0 || pair_cap > 0x7fffff00LL)
     return CNRMA_EINVAL;
-  if (workspace == nullptr || workspace_bytes < cnrma_sparse_conv_pairs_workspace_bytes(no_cap, K, Cout, pair_cap))
-    return CNRMA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  char* w = reinterpret_cast<char*>(workspace);
-  int32_t* hdr = reinterpret_cast<int32_t*>(w);        w += pairs_align(PAIR_HDR * 4);
-  int32_t* tile_tap = reinterpret_cast<int32_t*>(w);   w += pairs_align((size_t)(pair_cap / 128 + 1) * 4);
-  int32_t* pair_src = reinterpret_cast<int32_t*>(w);   w += pairs_align((size_t)pair_cap * 4);
-  int32_t* pos = reinterpret_cast<int32_t*>(w);        w += pairs_align((size_t)no_cap * K * 4);
-  float* prod = reinterpret_cast<float*>(w);
-  const hipError_t fe = cnrma_fill_bytes(hdr, 0, PAIR_HDR * 4, st);
-  if (fe != hipSuccess) return -(int)fe;
-  if (no_cap * K >= 0x7fffffffLL) return CNRMA_EINVAL;
-  const int64_t blocks = ceil_div(no_cap * K, 256 * PAIR_EPT);
-  hipLaunchKernelGGL(pairs_count_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, no_dev, K, hdr);
-  hipLaunchKernelGGL(pairs_plan_kernel, dim3(1), dim3(256), 0, st, K, hdr, tile_tap, pair_src, pair_cap);
-  hipLaunchKernelGGL(pairs_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, st, nbr, no_cap, no_dev, K, hdr, pair_src, pos,
-                     pair_cap);
-  CNRMA_LAUNCH_CHECK();
-  const int rc = launch_conv(in_feats, Cin, pair_src, 1, weight, Cout, nullptr, nullptr, nullptr, 0, prod, pair_cap, hdr + 64 + 33,
-                             1, nullptr, 0, st, nullptr, nullptr, 0, nullptr, 0, 0, nullptr, nullptr, tile_tap, K);
-  if (rc != 0) return rc;
-  ConvArgs p{};
-  p.K = K; p.Cout = Cout; p.scale = scale; p.shift = shift; p.residual = residual; p.act = act; p.out = out_feats;
-  p.no_cap = no_cap; p.no_dev = no_dev; p.out_amax = nullptr;
-  int64_t rb = ceil_div(no_cap * (Cout / 4), 256);
-  if (rb > 16384) rb = 16384;
-  if (K == 27) hipLaunchKernelGGL(pairs_reduce_kernel<27>, dim3((unsigned)rb), dim3(256), 0, st, p, pos, prod);
-  else hipLaunchKernelGGL(pairs_reduce_kernel<0>, dim3((unsigned)rb), dim3(256), 0, st, p, pos, prod);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
+  return launch_pairs(in_feats, nullptr, Cin, nbr, weight, nullptr,
+                      pairs_epilogue(K, Cout, scale, shift, residual, act, out_feats, nullptr, no_cap, no_dev), pair_cap, workspace,
+                      workspace_bytes, as_stream(stream));
 }
 
 // ---- second form of the gather-once kernel: instantiation table, work order, splits ---------------------------------------------
 constexpr int GO_FORM_DEFAULT = 1;      // the second form everywhere (scripts/go_forms.py, profiles/r05_go_forms2_*.log: 0.93x summed over
                                         // the layer classes of an S scene, never slower than the first form in its best work order)
-static int go_form_default(int64_t no_cap, int Cin, int Cout) { (void)no_cap; (void)Cin; (void)Cout; return GO_FORM_DEFAULT; }
 
 template <int WAVES_N, int KS, bool HAS_RES, int NB, bool STAMP = false, bool BF1 = false, bool APF = false>
 static int launch_go2_one(unsigned blocks, const ConvArgs& p, const GoArgs& g, const uint16_t* wfrag, const Go2Map& mp, hipStream_t st) {
@@ -4207,7 +4214,7 @@ struct Go2Plan { int form, bn, ks, splits, slices_per_split, mode, nb, apf; int6
 static Go2Plan go2_plan(int64_t no_cap, int Cin, int Cout, bool has_ws, size_t workspace_bytes) {
   const ConvTune tune = CNRMA_CONV_TUNE;
   Go2Plan pl{};
-  pl.form = tune.go >= 0 ? tune.go : go_form_default(no_cap, Cin, Cout);
+  pl.form = tune.go >= 0 ? tune.go : GO_FORM_DEFAULT;
   pl.bn = Cout >= 128 ? 128 : 64;
   pl.ks = pl.bn == 128 ? 1 : 2;
   pl.tiles = ceil_div(no_cap, GO_BM);
@@ -4263,11 +4270,7 @@ static int launch_go2(const Go2Plan& pl, ConvArgs p, GoArgs g, const uint16_t* w
     rc = pl.bn == 128 ? launch_go2_one<4, 1, false, 2, false, true>(blocks, p, g, wfrag, mp, st)
                       : launch_go2_one<2, 2, false, 2, false, true>(blocks, p, g, wfrag, mp, st);
     if (rc != 0) return rc;
-    if (pl.splits > 1) {
-      int64_t rb = ceil_div(p.no_cap * p.Cout / 4 + 1, 256);
-      if (rb > 4096) rb = 4096;
-      hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, p);
-    }
+    reduce_splits(p, st);
     CNRMA_LAUNCH_CHECK();
     return 0;
   }
@@ -4305,11 +4308,7 @@ static int launch_go2(const Go2Plan& pl, ConvArgs p, GoArgs g, const uint16_t* w
 #undef CNRMA_GO2
   }
   if (rc != 0) return rc;
-  if (pl.splits > 1) {
-    int64_t rb = ceil_div(p.no_cap * p.Cout / 4 + 1, 256);
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, p);
-  }
+  reduce_splits(p, st);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
@@ -4329,7 +4328,24 @@ extern "C" int cnrma_sparse_conv_go_plan(int64_t no_cap, int Cin, int Cout, size
   return 0;
 }
 
-static size_t go_align(size_t b) { return (b + 255) & ~(size_t)255; }
+// The tile-union buffer (tile_union_kernel), for ceil(no_cap / 64) output tiles: the tiles' headers [GO_HDR ints each], their
+// distinct input rows [GO_ROWS ints each], their local indices [27 x GO_BM uint16 each] -- one array after the other, each
+// padded to 256 bytes
+struct TileUnion { int32_t* hdr; int32_t* rows; uint16_t* lidx; size_t bytes; };
+static TileUnion tile_union_view(const void* buf, int64_t no_cap) {
+  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
+  const size_t hdr = align256(tiles * GO_HDR * 4), rows = align256(tiles * GO_ROWS * 4), lidx = align256(tiles * GO_BM * 27 * 2);
+  const uintptr_t b = reinterpret_cast<uintptr_t>(buf);
+  return {reinterpret_cast<int32_t*>(b), reinterpret_cast<int32_t*>(b + hdr), reinterpret_cast<uint16_t*>(b + hdr + rows),
+          hdr + rows + lidx};
+}
+
+static GoArgs go_args(const void* tile_union, int64_t no_cap) {
+  const TileUnion tu = tile_union_view(tile_union, no_cap);
+  GoArgs g;
+  g.hdr = tu.hdr; g.rows = tu.rows; g.lidx = tu.lidx; g.slices_per_split = 0; g.counters = nullptr;
+  return g;
+}
 
 // ---- exact-fp32 gather-once convolution: weight image, launcher -------------------------------------------------------------
 extern "C" size_t cnrma_sparse_conv_f32_frag_weight_bytes(int K, int Cin, int Cout) {
@@ -4340,8 +4356,7 @@ extern "C" int cnrma_sparse_conv_prepare_weights_f32_frag(const float* weight, i
                                                           void* stream) {
   if (weight == nullptr || weight_frag == nullptr || K <= 0 || Cin <= 0 || Cin % BK != 0 || Cout <= 0) return CNRMA_EINVAL;
   const int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  int64_t blocks = ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
+  int64_t blocks = capped_blocks(total, 4096);
   hipLaunchKernelGGL(prep_weights_f32_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<float*>(weight_frag), K, Cin, Cout);
   CNRMA_LAUNCH_CHECK();
@@ -4354,17 +4369,10 @@ extern "C" int cnrma_sparse_conv_go_f32(const float* in_feats, int Cin, const vo
   if (in_feats == nullptr || tile_union == nullptr || weight_frag == nullptr || out_feats == nullptr || Cin <= 0 || Cin % BK != 0 ||
       Cout < 64 || no_cap <= 0)
     return CNRMA_EINVAL;
-  const int K = 27;
   hipStream_t st = as_stream(stream);
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  const char* w = reinterpret_cast<const char*>(tile_union);
-  GoArgs g;
-  g.hdr = reinterpret_cast<const int32_t*>(w);      w += go_align(tiles * GO_HDR * 4);
-  g.rows = reinterpret_cast<const int32_t*>(w);     w += go_align(tiles * GO_ROWS * 4);
-  g.lidx = reinterpret_cast<const uint16_t*>(w);
-  g.counters = nullptr;
-  ConvArgs p{in_feats, Cin, nullptr, K, nullptr, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1, 1, K,
-             reinterpret_cast<float*>(workspace), nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
+  GoArgs g = go_args(tile_union, no_cap);
+  ConvArgs p = conv_args(in_feats, Cin, nullptr, 27, Cout, out_feats, no_cap, no_dev, workspace);
+  with_epilogue(p, scale, shift, residual, act);
   const Go2Plan pl = go2_plan(no_cap, Cin, Cout, workspace != nullptr, workspace_bytes);
   g.slices_per_split = pl.slices_per_split;
   p.splits = pl.splits;
@@ -4377,11 +4385,7 @@ extern "C" int cnrma_sparse_conv_go_f32(const float* in_feats, int Cin, const vo
     if (has_res) hipLaunchKernelGGL((sparse_conv_gof_kernel<2, 2, true>), dim3(pl.blocks), dim3(256), GOF_LDS, st, p, g, wf, pl.mp);
     else hipLaunchKernelGGL((sparse_conv_gof_kernel<2, 2, false>), dim3(pl.blocks), dim3(256), GOF_LDS, st, p, g, wf, pl.mp);
   }
-  if (pl.splits > 1) {
-    int64_t rb = ceil_div(no_cap * Cout / 4 + 1, 256);
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, p);
-  }
+  reduce_splits(p, st);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
@@ -4389,21 +4393,15 @@ extern "C" int cnrma_sparse_conv_go_f32(const float* in_feats, int Cin, const vo
 // ---- gather-once convolution: tile unions, fragment-order weights, launcher -----------------------------------------------
 
 extern "C" size_t cnrma_sparse_tile_union_bytes(int64_t no_cap) {
-  if (no_cap <= 0) return 0;
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  return go_align(tiles * GO_HDR * 4) + go_align(tiles * GO_ROWS * 4) + go_align(tiles * GO_BM * 27 * 2);
+  return no_cap <= 0 ? 0 : tile_union_view(nullptr, no_cap).bytes;
 }
 
 extern "C" int cnrma_sparse_tile_union_build(const int32_t* nbr, int64_t no_cap, const int32_t* no_dev, int K, void* tile_union,
                                              void* stream) {
   if (nbr == nullptr || tile_union == nullptr || no_cap <= 0 || K != 27) return CNRMA_EINVAL;
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  char* w = reinterpret_cast<char*>(tile_union);
-  int32_t* hdr = reinterpret_cast<int32_t*>(w);      w += go_align(tiles * GO_HDR * 4);
-  int32_t* rows = reinterpret_cast<int32_t*>(w);     w += go_align(tiles * GO_ROWS * 4);
-  uint16_t* lidx = reinterpret_cast<uint16_t*>(w);
-  hipLaunchKernelGGL(tile_union_kernel, dim3((unsigned)ceil_div((int64_t)tiles, 4)), dim3(256), 0, as_stream(stream), nbr, no_cap,
-                     no_dev, K, hdr, rows, lidx, CNRMA_CONV_TUNE.ablate);
+  const TileUnion tu = tile_union_view(tile_union, no_cap);
+  hipLaunchKernelGGL(tile_union_kernel, dim3((unsigned)ceil_div(ceil_div(no_cap, GO_BM), 4)), dim3(256), 0, as_stream(stream), nbr,
+                     no_cap, no_dev, K, tu.hdr, tu.rows, tu.lidx, CNRMA_CONV_TUNE.ablate);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
@@ -4414,14 +4412,11 @@ extern "C" int cnrma_sparse_conv_wgrad_go_bf16(const float* in_feats, int Cin, c
   if (in_feats == nullptr || tile_union == nullptr || grad_out == nullptr || slabs == nullptr || Cin <= 0 || Cout <= 0 ||
       (Cin & 3) || (Cout & 3) || no_cap <= 0 || parts <= 0)
     return CNRMA_EINVAL;
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  const char* w = reinterpret_cast<const char*>(tile_union);
-  const int32_t* hdr = reinterpret_cast<const int32_t*>(w);      w += go_align(tiles * GO_HDR * 4);
-  const int32_t* rows = reinterpret_cast<const int32_t*>(w);     w += go_align(tiles * GO_ROWS * 4);
-  const uint16_t* lidx = reinterpret_cast<const uint16_t*>(w);
+  const int64_t tiles = ceil_div(no_cap, GO_BM);
+  const TileUnion tu = tile_union_view(tile_union, no_cap);
   WgoMap map;
   map.parts = parts;
-  map.tiles_per_part = (int)ceil_div((int64_t)tiles, parts);
+  map.tiles_per_part = (int)ceil_div(tiles, parts);
   map.n_ci = (int)ceil_div(Cin, 64);
   map.n_co = (int)ceil_div(Cout, 64);
   map.by_part = parts >= 16;
@@ -4430,7 +4425,7 @@ extern "C" int cnrma_sparse_conv_wgrad_go_bf16(const float* in_feats, int Cin, c
   const int64_t blocks = (map.by_part ? ceil_div(parts, 8) * 8 : (int64_t)parts) * per;
   if (blocks > 0x7fffffffLL) return CNRMA_EINVAL;
   hipLaunchKernelGGL(conv_wgrad_go_kernel, dim3((unsigned)blocks), dim3(64 * (WGO_CW + WGO_PW)), 0, as_stream(stream), in_feats, Cin, grad_out, Cout,
-                     no_cap, no_dev, hdr, rows, lidx, slabs, map);
+                     no_cap, no_dev, tu.hdr, tu.rows, tu.lidx, slabs, map);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
@@ -4445,11 +4440,9 @@ extern "C" int cnrma_sparse_conv_prepare_weights_f16_frag(const float* weight, i
   float* amax = reinterpret_cast<float*>(wt + 2 * total) + 16;       // slot scratch behind the 64-byte trailer
   hipError_t e = cnrma_fill_bytes(amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
   if (e != hipSuccess) return -(int)e;
-  int64_t blocks = ceil_div(total_src / 4 + 1, 256);
-  if (blocks > 2048) blocks = 2048;
+  int64_t blocks = capped_blocks(total_src / 4 + 1, 2048);
   hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, total_src, nullptr, 1, amax);
-  blocks = ceil_div(total, 256);
-  if (blocks > 4096) blocks = 4096;
+  blocks = capped_blocks(total, 4096);
   hipLaunchKernelGGL(prep_weights_f16_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, wt, K, Cin, Cout, amax);
   CNRMA_LAUNCH_CHECK();
   return 0;
@@ -4506,8 +4499,7 @@ extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag_pair(const float* wei
   if (K <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BK != 0 || weight == nullptr || frag_forward == nullptr ||
       frag_transposed == nullptr)
     return CNRMA_EINVAL;
-  int64_t blocks = ceil_div((int64_t)K * Cin * conv_cout_padded(Cout) + (int64_t)K * Cout * conv_cout_padded(Cin), 256);
-  if (blocks > 8192) blocks = 8192;
+  int64_t blocks = capped_blocks((int64_t)K * Cin * conv_cout_padded(Cout) + (int64_t)K * Cout * conv_cout_padded(Cin), 8192);
   hipLaunchKernelGGL(prep_weights_bf16_frag_pair_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<__bf16*>(frag_forward), reinterpret_cast<__bf16*>(frag_transposed), K, Cin, Cout, flip ? 1 : 0);
   CNRMA_LAUNCH_CHECK();
@@ -4523,8 +4515,7 @@ extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag(const float* weight, 
   if (K <= 0 || Cin <= 0 || Cout <= 0 || (transpose ? Cout : Cin) % BK != 0 || weight == nullptr || weight_frag == nullptr)
     return CNRMA_EINVAL;
   const int Ci = transpose ? Cout : Cin, Co = transpose ? Cin : Cout;
-  int64_t blocks = ceil_div((int64_t)K * Ci * conv_cout_padded(Co), 256);
-  if (blocks > 4096) blocks = 4096;
+  int64_t blocks = capped_blocks((int64_t)K * Ci * conv_cout_padded(Co), 4096);
   hipLaunchKernelGGL(prep_weights_bf16_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<__bf16*>(weight_frag), K, Cin, Cout, transpose ? 1 : 0, flip ? 1 : 0);
   CNRMA_LAUNCH_CHECK();
@@ -4537,18 +4528,9 @@ extern "C" int cnrma_sparse_conv_go_bf16(const float* in_feats, int Cin, const v
   if (in_feats == nullptr || tile_union == nullptr || weight_frag == nullptr || out_feats == nullptr || Cin <= 0 || Cin % BK != 0 ||
       Cout < 64 || no_cap <= 0)
     return CNRMA_EINVAL;
-  const int K = 27;
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  const char* w = reinterpret_cast<const char*>(tile_union);
-  GoArgs g;
-  g.hdr = reinterpret_cast<const int32_t*>(w);      w += go_align(tiles * GO_HDR * 4);
-  g.rows = reinterpret_cast<const int32_t*>(w);     w += go_align(tiles * GO_ROWS * 4);
-  g.lidx = reinterpret_cast<const uint16_t*>(w);
-  ConvArgs p{in_feats, Cin, nullptr, K, nullptr, Cout, nullptr, nullptr, nullptr, 0, out_feats, no_cap, no_dev, 1, 1, K,
-             reinterpret_cast<float*>(workspace), nullptr, 0, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0};
-  p.ablate = 0;
+  const ConvArgs p = conv_args(in_feats, Cin, nullptr, 27, Cout, out_feats, no_cap, no_dev, workspace);
   const Go2Plan pl = go2_plan(no_cap, Cin, Cout, workspace != nullptr, workspace_bytes);
-  return launch_go2(pl, p, g, reinterpret_cast<const uint16_t*>(weight_frag), false, nullptr, as_stream(stream), true);
+  return launch_go2(pl, p, go_args(tile_union, no_cap), reinterpret_cast<const uint16_t*>(weight_frag), false, nullptr, as_stream(stream), true);
 }
 
 extern "C" int cnrma_sparse_conv_go_f16x3(const float* in_feats, const float* in_amax, int Cin, const void* tile_union,
@@ -4561,73 +4543,20 @@ extern "C" int cnrma_sparse_conv_go_f16x3(const float* in_feats, const float* in
     return CNRMA_EINVAL;
   const int K = 27;
   hipStream_t st = as_stream(stream);
-  const size_t tiles = (size_t)ceil_div(no_cap, GO_BM);
-  const char* w = reinterpret_cast<const char*>(tile_union);
-  GoArgs g;
-  g.hdr = reinterpret_cast<const int32_t*>(w);      w += go_align(tiles * GO_HDR * 4);
-  g.rows = reinterpret_cast<const int32_t*>(w);     w += go_align(tiles * GO_ROWS * 4);
-  g.lidx = reinterpret_cast<const uint16_t*>(w);
-  ConvArgs p{in_feats, Cin, nullptr, K, nullptr, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1, 1, K,
-             reinterpret_cast<float*>(workspace), nullptr, 0, nullptr, 0, in_amax, nullptr, out_amax, nullptr, 0};
+  const GoArgs g = go_args(tile_union, no_cap);
+  ConvArgs p = conv_args(in_feats, Cin, nullptr, K, Cout, out_feats, no_cap, no_dev, workspace);
+  with_epilogue(p, scale, shift, residual, act);
+  p.in_amax = in_amax; p.out_amax = out_amax;
   p.ablate = CNRMA_CONV_TUNE.ablate;
   const uint16_t* wfrag = reinterpret_cast<const uint16_t*>(weight_frag);
   p.w_amax = reinterpret_cast<const float*>(wfrag + 2 * (int64_t)K * Cin * conv_cout_padded(Cout));
-  const int bn = Cout >= 128 ? 128 : 64;
-  const int ns = Cin / BK;
-  {
-    const Go2Plan pl = go2_plan(no_cap, Cin, Cout, workspace != nullptr, workspace_bytes);
-#ifndef CNRMA_EXPERIMENTS
-    (void)ns; (void)bn; (void)tiles;
-    return launch_go2(pl, p, g, wfrag, residual != nullptr, nullptr, st);       // the product library: the second form, nothing else
-  }
-}
+  const Go2Plan pl = go2_plan(no_cap, Cin, Cout, workspace != nullptr, workspace_bytes);
+#ifdef CNRMA_EXPERIMENTS
+  return launch_go_experiments(pl, p, g, wfrag, workspace_bytes, tile_counters, st);
 #else
-    // the other ablation masks (diagnostic kernels with phases switched off) exist in the first form only
-    if (pl.form >= 2 && (CNRMA_CONV_TUNE.ablate & ~64) == 0 && (uint64_t)no_cap * (uint64_t)Cin * 4u < (1ull << 32))
-      return launch_go3(pl, p, g, wfrag, residual != nullptr, (CNRMA_CONV_TUNE.ablate & 64) ? tile_counters : nullptr, st);
-    if (pl.form >= 1 && (CNRMA_CONV_TUNE.ablate & ~64) == 0)
-      return launch_go2(pl, p, g, wfrag, residual != nullptr, (CNRMA_CONV_TUNE.ablate & 64) ? tile_counters : nullptr, st);
-  }
-  // short layers: split over the 32-channel slices (every block still runs all 27 offsets of its slices); partial slabs are
-  // reduced by conv_reduce_kernel in a fixed order
-  int splits = 1;
-  const int64_t blocks = (int64_t)tiles * ceil_div(Cout, bn);
-  const int force = CNRMA_CONV_TUNE.splits;
-  if (workspace != nullptr && ns > 1 && (blocks < 384 || force > 0)) {
-    splits = force > 0 ? force : (int)ceil_div(768, blocks);
-    if (splits > ns) splits = ns;
-    const size_t per = (size_t)no_cap * Cout * sizeof(float);
-    if (per > 0 && (size_t)splits * per > workspace_bytes) splits = (int)(workspace_bytes / per);
-    if (splits < 2) splits = 1;
-  }
-  g.slices_per_split = (int)ceil_div(ns, splits);
-  splits = (int)ceil_div(ns, g.slices_per_split);
-  p.splits = splits;
-  g.counters = splits > 1 ? reinterpret_cast<unsigned*>(tile_counters) : nullptr;
-  const bool has_res = residual != nullptr && splits == 1;
-  dim3 grid((unsigned)tiles, (unsigned)ceil_div(Cout, bn), (unsigned)splits);
-  if (p.ablate != 0 && !has_res) {                         // diagnostic instantiations (timing experiments only)
-    if (bn == 128) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, false, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
-    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, false, 2, true>), grid, dim3(256), 0, st, p, g, wfrag);
-  } else if (bn == 128) {
-    if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
-    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, false>), grid, dim3(256), 0, st, p, g, wfrag);
-  } else {
-    if (CNRMA_CONV_TUNE.pf == 3) {                             // A/B aid: the 2 x 2 waves-over-rows-x-columns form
-      if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<2, 2, 1, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
-      else hipLaunchKernelGGL((sparse_conv_go_kernel<2, 2, 1, 1, false>), grid, dim3(256), 0, st, p, g, wfrag);
-    } else if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, true, 2>), grid, dim3(256), 0, st, p, g, wfrag);
-    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, false, 2>), grid, dim3(256), 0, st, p, g, wfrag);
-  }
-  if (splits > 1 && g.counters == nullptr) {
-    int64_t rb = ceil_div(no_cap * Cout / 4 + 1, 256);
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, p);
-  }
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
+  return launch_go2(pl, p, g, wfrag, residual != nullptr, nullptr, st);      // the product library: the second form, nothing else
 #endif
+}
 
 extern "C" int cnrma_sparse_conv_f16x3(const float* in_feats, const float* in_amax, int Cin, const int32_t* nbr, int K,
                                        const void* weight_split, int Cout, const float* scale, const float* shift,
@@ -4635,9 +4564,9 @@ extern "C" int cnrma_sparse_conv_f16x3(const float* in_feats, const float* in_am
                                        int64_t no_cap, const int32_t* no_dev, void* workspace, size_t workspace_bytes,
                                        void* stream) {
   if (weight_split == nullptr || Cin % 32 != 0 || in_feats == nullptr || in_amax == nullptr) return CNRMA_EINVAL;
-  return launch_conv(in_feats, Cin, nbr, K, nullptr, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1,
-                     workspace, workspace_bytes, as_stream(stream), weight_split, nullptr, 0, nullptr, 0, 1, in_amax,
-                     out_amax);
+  ConvArgs p = conv_args(in_feats, Cin, nbr, K, Cout, out_feats, no_cap, no_dev, workspace);
+  p.in_amax = in_amax; p.out_amax = out_amax;
+  return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_F16X3, weight_split, workspace_bytes, as_stream(stream));
 }
 
 extern "C" size_t cnrma_sparse_conv_bf16_weight_bytes(int K, int Cin, int Cout) {
@@ -4647,8 +4576,7 @@ extern "C" size_t cnrma_sparse_conv_bf16_weight_bytes(int K, int Cin, int Cout) 
 extern "C" int cnrma_sparse_conv_prepare_weights_bf16(const float* weight, int K, int Cin, int Cout, void* weight_bf16,
                                                       void* stream) {
   if (K <= 0 || Cin <= 0 || Cout <= 0 || weight_bf16 == nullptr) return CNRMA_EINVAL;
-  int64_t blocks = ceil_div((int64_t)K * Cin * conv_cout_padded(Cout), 256);
-  if (blocks > 4096) blocks = 4096;
+  int64_t blocks = capped_blocks((int64_t)K * Cin * conv_cout_padded(Cout), 4096);
   hipLaunchKernelGGL(prep_weights_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<__bf16*>(weight_bf16), K, Cin, Cout);
   CNRMA_LAUNCH_CHECK();
@@ -4658,8 +4586,7 @@ extern "C" int cnrma_sparse_conv_prepare_weights_bf16(const float* weight, int K
 extern "C" int cnrma_sparse_conv_prepare_weights_bf16_t(const float* weight, int K, int Cin, int Cout, int flip,
                                                         void* weight_bf16, void* stream) {
   if (K <= 0 || Cin <= 0 || Cout <= 0 || Cout % 32 != 0 || weight == nullptr || weight_bf16 == nullptr) return CNRMA_EINVAL;
-  int64_t blocks = ceil_div((int64_t)K * Cout * conv_cout_padded(Cin), 256);
-  if (blocks > 4096) blocks = 4096;
+  int64_t blocks = capped_blocks((int64_t)K * Cout * conv_cout_padded(Cin), 4096);
   hipLaunchKernelGGL(prep_weights_bf16_t_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
                      reinterpret_cast<__bf16*>(weight_bf16), K, Cin, Cout, flip ? 1 : 0);
   CNRMA_LAUNCH_CHECK();
@@ -4671,8 +4598,16 @@ extern "C" int cnrma_sparse_conv_bf16(const float* in_feats, int Cin, const int3
                                       float* out_feats, int64_t no_cap, const int32_t* no_dev, void* workspace,
                                       size_t workspace_bytes, void* stream) {
   if (weight_bf16 == nullptr || Cin % 32 != 0 || in_feats == nullptr) return CNRMA_EINVAL;
-  return launch_conv(in_feats, Cin, nbr, K, nullptr, Cout, scale, shift, residual, act, out_feats, no_cap, no_dev, 1,
-                     workspace, workspace_bytes, as_stream(stream), weight_bf16, nullptr, 0, nullptr, 0, 2);
+  ConvArgs p = conv_args(in_feats, Cin, nbr, K, Cout, out_feats, no_cap, no_dev, workspace);
+  return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_BF16, weight_bf16, workspace_bytes, as_stream(stream));
+}
+
+// generative transpose (k2 s2): 8 weight slices; slice k reads in[i] (identity map, K = 1) and writes row 8 i + morton_child(k)
+static ConvArgs convtr_args(const float* in, int Cin, int Cout, const float* scale, const float* shift, int act, float* out,
+                            int64_t n_cap, const int32_t* n_dev) {
+  ConvArgs p = conv_args(in, Cin, nullptr, 1, Cout, out, n_cap, n_dev);
+  p.slices = 8;
+  return with_epilogue(p, scale, shift, nullptr, act);
 }
 
 extern "C" int cnrma_sparse_convtr_gen_f16x3(const int32_t* in_coords, const float* in_feats, const float* in_amax,
@@ -4684,8 +4619,9 @@ extern "C" int cnrma_sparse_convtr_gen_f16x3(const int32_t* in_coords, const flo
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(convtr_coords_kernel, dim3((unsigned)ceil_div(n_cap * 8, 256)), dim3(256), 0, st, in_coords,
                      n_cap, n_dev, half_stride, out_coords);
-  return launch_conv(in_feats, Cin, nullptr, 1, nullptr, Cout, scale, shift, nullptr, act, out_feats, n_cap, n_dev, 8,
-                     nullptr, 0, st, weight_split, nullptr, 0, nullptr, 0, 1, in_amax, out_amax);
+  ConvArgs p = convtr_args(in_feats, Cin, Cout, scale, shift, act, out_feats, n_cap, n_dev);
+  p.in_amax = in_amax; p.out_amax = out_amax;
+  return launch_conv(p, CONV_F16X3, weight_split, 0, st);
 }
 
 extern "C" int cnrma_sparse_split_features(const float* feats, int64_t n_cap, const int32_t* n_dev, int C,
@@ -4707,8 +4643,10 @@ extern "C" int cnrma_sparse_convtr_gen_bf16x6(const int32_t* in_coords, const fl
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(convtr_coords_kernel, dim3((unsigned)ceil_div(n_cap * 8, 256)), dim3(256), 0, st, in_coords,
                      n_cap, n_dev, half_stride, out_coords);
-  return launch_conv(in_feats, Cin, nullptr, 1, nullptr, Cout, scale, shift, nullptr, act, out_feats, n_cap, n_dev, 8,
-                     nullptr, 0, st, weight_split, in_split, n_cap, out_split, 8 * n_cap);
+  ConvArgs p = convtr_args(in_feats, Cin, Cout, scale, shift, act, out_feats, n_cap, n_dev);
+  p.in_split = reinterpret_cast<const uint16_t*>(in_split); p.in_zero_row = n_cap;
+  p.out_split = reinterpret_cast<uint16_t*>(out_split); p.out_zero_row = 8 * n_cap;
+  return launch_conv(p, CONV_EXACT, weight_split, 0, st);
 }
 
 extern "C" int cnrma_sparse_convtr_gen_f32(const int32_t* in_coords, const float* in_feats, int64_t n_cap,
@@ -4719,9 +4657,9 @@ extern "C" int cnrma_sparse_convtr_gen_f32(const int32_t* in_coords, const float
   hipStream_t st = as_stream(stream);
   hipLaunchKernelGGL(convtr_coords_kernel, dim3((unsigned)ceil_div(n_cap * 8, 256)), dim3(256), 0, st, in_coords,
                      n_cap, n_dev, half_stride, out_coords);
-  // 8 weight slices; slice k reads in[i] (identity map, K = 1) and writes row k*n + i
-  return launch_conv(in_feats, Cin, nullptr, 1, weight, Cout, scale, shift, nullptr, act, out_feats, n_cap, n_dev, 8,
-                     nullptr, 0, st);
+  ConvArgs p = convtr_args(in_feats, Cin, Cout, scale, shift, act, out_feats, n_cap, n_dev);
+  p.weight = weight;
+  return launch_conv(p, CONV_EXACT, nullptr, 0, st);
 }
 
 extern "C" int cnrma_sparse_maxpool_f32(const float* in_feats, int C, const int32_t* nbr, int K, float* out_feats,

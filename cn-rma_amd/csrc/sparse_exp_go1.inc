@@ -323,3 +323,43 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_go_kernel(ConvArgs p, GoAr
   }
 }
 
+
+// the first form's launcher (p, g: the layer as cnrma_sparse_conv_go_f16x3 prepared it).  Short layers: split over the 32-channel
+// slices (every block still runs all 27 offsets of its slices); the partial slabs are reduced by conv_reduce_kernel in a fixed
+// order, or in the kernel when arrival counters are handed over
+static int launch_go1(ConvArgs p, GoArgs g, const uint16_t* wfrag, size_t workspace_bytes, void* tile_counters, hipStream_t st) {
+  const int64_t no_cap = p.no_cap, tiles = ceil_div(no_cap, GO_BM);
+  const int Cout = p.Cout, bn = Cout >= 128 ? 128 : 64, ns = p.Cin / BK;
+  int splits = 1;
+  const int64_t blocks = tiles * ceil_div(Cout, bn);
+  const int force = CNRMA_CONV_TUNE.splits;
+  if (p.slab != nullptr && ns > 1 && (blocks < 384 || force > 0)) {
+    splits = force > 0 ? force : (int)ceil_div(768, blocks);
+    if (splits > ns) splits = ns;
+    const size_t per = (size_t)no_cap * Cout * sizeof(float);
+    if (per > 0 && (size_t)splits * per > workspace_bytes) splits = (int)(workspace_bytes / per);
+    if (splits < 2) splits = 1;
+  }
+  g.slices_per_split = (int)ceil_div(ns, splits);
+  splits = (int)ceil_div(ns, g.slices_per_split);
+  p.splits = splits;
+  g.counters = splits > 1 ? reinterpret_cast<unsigned*>(tile_counters) : nullptr;
+  const bool has_res = p.residual != nullptr && splits == 1;
+  dim3 grid((unsigned)tiles, (unsigned)ceil_div(Cout, bn), (unsigned)splits);
+  if (p.ablate != 0 && !has_res) {                         // diagnostic instantiations (timing experiments only)
+    if (bn == 128) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, false, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
+    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, false, 2, true>), grid, dim3(256), 0, st, p, g, wfrag);
+  } else if (bn == 128) {
+    if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
+    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 4, 2, 1, false>), grid, dim3(256), 0, st, p, g, wfrag);
+  } else {
+    if (CNRMA_CONV_TUNE.pf == 3) {                             // A/B aid: the 2 x 2 waves-over-rows-x-columns form
+      if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<2, 2, 1, 1, true>), grid, dim3(256), 0, st, p, g, wfrag);
+      else hipLaunchKernelGGL((sparse_conv_go_kernel<2, 2, 1, 1, false>), grid, dim3(256), 0, st, p, g, wfrag);
+    } else if (has_res) hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, true, 2>), grid, dim3(256), 0, st, p, g, wfrag);
+    else hipLaunchKernelGGL((sparse_conv_go_kernel<1, 2, 2, 1, false, 2>), grid, dim3(256), 0, st, p, g, wfrag);
+  }
+  if (g.counters == nullptr) reduce_splits(p, st);
+  CNRMA_LAUNCH_CHECK();
+  return 0;
+}

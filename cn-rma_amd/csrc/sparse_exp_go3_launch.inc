@@ -35,12 +35,20 @@ static int launch_go3(const Go2Plan& pl, ConvArgs p, GoArgs g, const uint16_t* w
   else if (pl.bn == 128) rc = has_res ? launch_go3_one<4, 1, true>(blocks, p, g, wfrag, mp, st) : launch_go3_one<4, 1, false>(blocks, p, g, wfrag, mp, st);
   else rc = has_res ? launch_go3_one<2, 2, true>(blocks, p, g, wfrag, mp, st) : launch_go3_one<2, 2, false>(blocks, p, g, wfrag, mp, st);
   if (rc != 0) return rc;
-  if (pl.splits > 1) {
-    int64_t rb = ceil_div(p.no_cap * p.Cout / 4 + 1, 256);
-    if (rb > 4096) rb = 4096;
-    hipLaunchKernelGGL(conv_reduce_kernel, dim3((unsigned)rb), dim3(256), 0, st, p);
-  }
+  reduce_splits(p, st);
   CNRMA_LAUNCH_CHECK();
   return 0;
+}
+
+// cnrma_sparse_conv_go_f16x3 in the experiments library: the form cnrma_debug_conv_tuning selects (third, second or first); the
+// ablation masks other than the stamps (64) exist in the first form only
+static int launch_go_experiments(const Go2Plan& pl, const ConvArgs& p, const GoArgs& g, const uint16_t* wfrag, size_t workspace_bytes,
+                                 void* tile_counters, hipStream_t st) {
+  const bool plain = (p.ablate & ~64) == 0;
+  void* stamps = (p.ablate & 64) ? tile_counters : nullptr;
+  if (pl.form >= 2 && plain && (uint64_t)p.no_cap * (uint64_t)p.Cin * 4u < (1ull << 32))
+    return launch_go3(pl, p, g, wfrag, p.residual != nullptr, stamps, st);
+  if (pl.form >= 1 && plain) return launch_go2(pl, p, g, wfrag, p.residual != nullptr, stamps, st);
+  return launch_go1(p, g, wfrag, workspace_bytes, tile_counters, st);
 }
 

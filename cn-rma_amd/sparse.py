@@ -479,15 +479,19 @@ _WS_STREAMS = 12      # scratch buffers kept: the streams of a process come and 
                       # back to the stream it was allocated on, in stream order.
 
 
+_LRU_LOCK = threading.RLock()      # the tables are module-wide; several host threads (one per scene slot) reach them
+
+
 def _lru_get(table, key, make, limit=_WS_STREAMS):
     """table[key] (moved to the most-recent end), created by make() when absent; the oldest entries beyond `limit` are dropped"""
-    buf = table.pop(key, None)
-    if buf is None:
-        buf = make()
-    table[key] = buf
-    while len(table) > limit:
-        table.pop(next(iter(table)))
-    return buf
+    with _LRU_LOCK:
+        buf = table.pop(key, None)
+        if buf is None:
+            buf = make()
+        table[key] = buf
+        while len(table) > limit:
+            table.pop(next(iter(table)))
+        return buf
 
 
 def _workspace(nbytes, device):
@@ -496,10 +500,11 @@ def _workspace(nbytes, device):
     if P.static():
         return P.current().workspace(nbytes, device)
     key = (device, stream())
-    buf = _WS.pop(key, None)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-    return _lru_get(_WS, key, lambda: buf)
+    with _LRU_LOCK:
+        buf = _WS.pop(key, None)
+        if buf is None or buf.numel() < nbytes:
+            buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
+        return _lru_get(_WS, key, lambda: buf)
 
 
 _COUNTER_WORDS = 16384
@@ -587,83 +592,68 @@ def _pinned(ws):
     return ws
 
 
-def split_weights_f16(weight):
-    """weight fp32 [K,Cin,Cout] (or [Cin,Cout]) -> fp16 [2,K,Cout,Cin] (hi / lo pieces of weight * 2^s) + a trailer word
-    holding max|weight| (the kernel derives s from it).  Cached on the weight tensor like split_weights()."""
+def _cached_image(weight, kind):
+    """(tag, cached entry or None): the entry when it was made from the weight's current contents"""
     tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_split_f16")
-    if hit is not None and hit[0] == tag:
+    hit = _cache_get(weight, kind)
+    return tag, (hit if hit is not None and hit[0] == tag else None)
+
+
+def _weight_image(weight, kind, nbytes, entry, *args):
+    """the prepared image `kind` of a weight fp32 [K,Cin,Cout] (or [Cin,Cout]): `nbytes` = the library's bytes query, `entry` =
+    its prepare entry point (called with the weight, K, Cin, Cout, *args, the image).  Cached on the weight tensor object (so it
+    dies with it) and rebuilt when the tensor is modified in place or moved."""
+    tag, hit = _cached_image(weight, kind)
+    if hit is not None:
         return _pinned(hit[1])
     w = weight.detach().contiguous().float()
     if w.dim() == 2:
         w = w.unsqueeze(0)
     K, Cin, Cout = w.shape
-    ws = torch.empty(_lib.load().cnrma_sparse_conv_f16_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-    call("cnrma_sparse_conv_prepare_weights_f16", ptr(w), K, Cin, Cout, ptr(ws), stream())
-    _cache_put(weight, "_cnrma_split_f16", (tag, ws))
+    ws = torch.empty(getattr(_lib.load(), nbytes)(K, Cin, Cout), dtype=torch.uint8, device=w.device)
+    call(entry, ptr(w), K, Cin, Cout, *args, ptr(ws), stream())
+    _cache_put(weight, kind, (tag, ws))
     return _pinned(ws)
+
+
+def split_weights(weight):
+    """bf16 [3,K,Cout_p,Cin] (hi / mid / lo pieces, Cout padded to 128): the "bf16x6" convolutions"""
+    return _weight_image(weight, "_cnrma_split", "cnrma_sparse_conv_weight_bytes", "cnrma_sparse_conv_prepare_weights")
+
+
+def split_weights_f16(weight):
+    """fp16 [2,K,Cout,Cin] (hi / lo pieces of weight * 2^s) + a trailer word holding max|weight| (the kernel derives s from it)"""
+    return _weight_image(weight, "_cnrma_split_f16", "cnrma_sparse_conv_f16_weight_bytes", "cnrma_sparse_conv_prepare_weights_f16")
 
 
 def split_weights_f16_frag(weight):
-    """weight fp32 [27,Cin,Cout] -> the fp16 hi / lo image in MFMA-fragment order (gather-once convolution), cached like
-    split_weights_f16()"""
-    tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_frag_f16")
-    if hit is not None and hit[0] == tag:
-        return _pinned(hit[1])
-    w = weight.detach().contiguous().float()
-    K, Cin, Cout = w.shape
-    ws = torch.empty(_lib.load().cnrma_sparse_conv_f16_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-    call("cnrma_sparse_conv_prepare_weights_f16_frag", ptr(w), K, Cin, Cout, ptr(ws), stream())
-    _cache_put(weight, "_cnrma_frag_f16", (tag, ws))
-    return _pinned(ws)
+    """[27,Cin,Cout] -> the fp16 hi / lo image in MFMA-fragment order (gather-once convolution)"""
+    return _weight_image(weight, "_cnrma_frag_f16", "cnrma_sparse_conv_f16_weight_bytes",
+                         "cnrma_sparse_conv_prepare_weights_f16_frag")
 
 
 def weights_f32_frag(weight):
-    """weight fp32 [27,Cin,Cout] -> the fp32 image in MFMA-fragment order (exact-fp32 gather-once convolution), cached like
-    split_weights_f16()"""
-    tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_frag_f32")
-    if hit is not None and hit[0] == tag:
-        return _pinned(hit[1])
-    w = weight.detach().contiguous().float()
-    K, Cin, Cout = w.shape
-    ws = torch.empty(_lib.load().cnrma_sparse_conv_f32_frag_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-    call("cnrma_sparse_conv_prepare_weights_f32_frag", ptr(w), K, Cin, Cout, ptr(ws), stream())
-    _cache_put(weight, "_cnrma_frag_f32", (tag, ws))
-    return _pinned(ws)
+    """[27,Cin,Cout] -> the fp32 image in MFMA-fragment order (exact-fp32 gather-once convolution)"""
+    return _weight_image(weight, "_cnrma_frag_f32", "cnrma_sparse_conv_f32_frag_weight_bytes",
+                         "cnrma_sparse_conv_prepare_weights_f32_frag")
 
 
 def weights_bf16(weight):
-    """weight fp32 [K,Cin,Cout] (or [Cin,Cout]) -> bf16 [K,Cout_p,Cin] (round to nearest) for the "bf16" convolutions;
-    cached on the weight tensor like the other prepared images"""
-    tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_bf16")
-    if hit is not None and hit[0] == tag:
-        return _pinned(hit[1])
-    w = weight.detach().contiguous().float()
-    if w.dim() == 2:
-        w = w.unsqueeze(0)
-    K, Cin, Cout = w.shape
-    ws = torch.empty(_lib.load().cnrma_sparse_conv_bf16_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-    call("cnrma_sparse_conv_prepare_weights_bf16", ptr(w), K, Cin, Cout, ptr(ws), stream())
-    _cache_put(weight, "_cnrma_bf16", (tag, ws))
-    return _pinned(ws)
+    """bf16 [K,Cout_p,Cin] (round to nearest) for the "bf16" convolutions"""
+    return _weight_image(weight, "_cnrma_bf16", "cnrma_sparse_conv_bf16_weight_bytes", "cnrma_sparse_conv_prepare_weights_bf16")
 
 
 def weights_bf16_frag(weight, transposed=False):
     """weight fp32 [27,Cin,Cout] -> the bf16 MFMA-fragment image of cnrma_sparse_conv_go_bf16 (transposed: the mirrored +
     transposed image of the data gradient); cached on the weight tensor.  When both widths allow it the two images are made
     by ONE launch at the first request of a step -- the forward's, whose host-bound launch stream has room for it"""
-    tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_bf16_frag")
-    if hit is not None and hit[0] == tag and hit[1 + int(transposed)] is not None:
-        return _pinned(hit[1 + int(transposed)])
+    tag, hit = _cached_image(weight, "_cnrma_bf16_frag")
+    fwd, tr = hit[1:] if hit is not None else (None, None)
+    if (tr if transposed else fwd) is not None:
+        return _pinned(tr if transposed else fwd)
     w = weight.detach().contiguous().float()
     K, Cin, Cout = w.shape
     lib = _lib.load()
-    fwd = hit[1] if hit is not None and hit[0] == tag else None
-    tr = hit[2] if hit is not None and hit[0] == tag else None
     if Cin % 32 == 0 and Cout % 32 == 0 and Cin >= 64 and fwd is None and tr is None:
         fwd = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
         tr = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cout, Cin), dtype=torch.uint8, device=w.device)
@@ -688,23 +678,7 @@ def _precision(precision=None):
     return CONV_PRECISION
 
 
-def split_weights(weight):
-    """weight fp32 [K,Cin,Cout] (or [Cin,Cout]) -> bf16 [3,K,Cout_p,Cin] (hi / mid / lo pieces, Cout padded to 128).  The result is cached ON
-    the weight tensor object (so it dies with it) and rebuilt when the tensor is modified in place or moved."""
-    tag = (weight._version, weight.data_ptr(), weight.device)
-    hit = _cache_get(weight, "_cnrma_split")
-    if hit is not None and hit[0] == tag:
-        return _pinned(hit[1])
-    w = weight.detach().contiguous().float()
-    if w.dim() == 2:
-        w = w.unsqueeze(0)
-    K, Cin, Cout = w.shape
-    ws = torch.empty(_lib.load().cnrma_sparse_conv_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-    call("cnrma_sparse_conv_prepare_weights", ptr(w), K, Cin, Cout, ptr(ws), stream())
-    _cache_put(weight, "_cnrma_split", (tag, ws))
-    return _pinned(ws)
-
-
+_STAGE_IMAGE = {"bf16": weights_bf16, "f16x3": split_weights_f16, "bf16x6": split_weights}    # prepared image of each precision
 CONV_MODES = {"f32": 0, "f16x3": 1, "bf16": 2, "bf16x6": 3}
 CONV_SHAPES = ("128x128", "128x64", "64x64", "128x32", "64x128", "256x128", "256x64")
 
@@ -726,7 +700,7 @@ def conv_go_plan(n_out, Cin, Cout, residual=False):
     dict(form, columns, ks, splits, slices_per_split, order, residual_in_kernel, blocks, offsets_in_flight, workspace) --
     cnrma_sparse_conv_go_plan, a pure host function"""
     import ctypes
-    ws = n_out * Cout * 4 * (Cin // 32) if n_out < GO_WS_ROWS else 0
+    ws = _go_ws_bytes(n_out, Cin, Cout)
     out = (ctypes.c_int * 8)()
     call("cnrma_sparse_conv_go_plan", int(n_out), int(Cin), int(Cout), ws, int(bool(residual)), out)
     return dict(form=out[0], columns=out[1], ks=2 if out[1] == 64 else 1, splits=out[2], slices_per_split=out[3],
@@ -825,81 +799,115 @@ def conv(x, weight, kernel_size=3, stride=1, scale=None, shift=None, residual=No
     else:
         nbr = in_cs.neighbours(out_cs, kernel_size, in_cs.stride)
     out = torch.empty((out_cs.n, Cout), dtype=torch.float32, device=x.device)
-    out_split = None
+    out_split = out_amax = None
     if out_cs.n:
         res = residual.F.contiguous() if isinstance(residual, SparseTensor) else residual
         if res is not None:
             assert res.shape == out.shape
         ws_bytes = _lib.load().cnrma_sparse_conv_workspace_bytes(out_cs.n, Cout, K)
         ws = _workspace(ws_bytes, x.device) if ws_bytes else None
-        prec = _precision(precision)
+        prec = _precision(precision) if Cin % 32 == 0 else "f32"      # layers with Cin % 32 != 0 always run in fp32
         if P.static():       # the captured launches keep raw pointers: pin what the modules' caches may drop
             P.current().keep(weight, w, scale, shift)
-        if prec == "bf16" and Cin % 32 == 0:
-            call("cnrma_sparse_conv_bf16", ptr(x.F.contiguous()), Cin, ptr(nbr), K, ptr(weights_bf16(weight)), Cout, ptr(scale),
-                 ptr(shift), ptr(res), ACT[act], ptr(out), out_cs.n, ptr(out_cs.n_dev), ptr(ws), ws_bytes, stream())
-            return SparseTensor(out, out_cs)
-        if prec == "f16x3" and Cin % 32 == 0:
+        if prec == "f16x3":
             out_amax = _amax_slot(x.device)
+        # the kernel family: pair list, gather-once or the stage kernel.  _nearly_empty_map and _gather_once consume recorded
+        # plan flags: each is asked under exactly these conditions, in this order
+        family = "stage"
+        if prec in ("f16x3", "f32") and Cin % 32 == 0:
             if PAIR_CONV and stride == 2 and K == 27 and Cout % 4 == 0 and Cin >= PAIR_CONV_MIN_CIN and _nearly_empty_map(in_cs, out_cs):
-                # pair-list kernel: the kernel map of a stride-2 convolution on a point sample is ~5 % full
-                pair_cap = (min(27 * out_cs.n, 8 * in_cs.n) + 128 * K + 127) // 128 * 128
-                pw_bytes = _lib.load().cnrma_sparse_conv_pairs_workspace_bytes(out_cs.n, K, Cout, pair_cap)
-                pw = _workspace(pw_bytes, x.device)
-                call("cnrma_sparse_conv_pairs_f16x3", ptr(x.F.contiguous()), ptr(x.absmax()), Cin, ptr(nbr), K,
-                     ptr(split_weights_f16(weight)), Cout, ptr(scale), ptr(shift), ptr(res), ACT[act], ptr(out), ptr(out_amax),
-                     out_cs.n, ptr(out_cs.n_dev), pair_cap, ptr(pw), pw_bytes, stream())
-                if P.static():
-                    # the kernels flag pair entries dropped for want of capacity in word 98 of the workspace header (the
-                    # capacity above is the provable bound, so this never fires; a violated assumption must still never be
-                    # silent: the word joins the plan's status -- copied out, the workspace is reused by the next layer)
-                    P.current().watch(pw[:PAIR_HDR_BYTES].view(torch.int32)[PAIR_OVERFLOW_WORD:PAIR_OVERFLOW_WORD + 1].clone(), 0, 0)
-                return SparseTensor(out, out_cs, None, out_amax)
-            if K == 27 and stride == 1 and Cout >= 64 and _gather_once(in_cs, out_cs):
-                # gather-once kernel: a tile's distinct input rows staged once per channel slice, offsets run from LDS
-                go_ws_bytes = out_cs.n * Cout * 4 * (Cin // 32) if out_cs.n < GO_WS_ROWS else 0
-                go_ws = _workspace(go_ws_bytes, x.device) if go_ws_bytes else None
-                counters = _tile_counters(x.device) if GO_INKERNEL_REDUCE and go_ws_bytes and \
-                    -(-out_cs.n // 64) * -(-Cout // 64) <= _COUNTER_WORDS else GO_STAMPS
-                call("cnrma_sparse_conv_go_f16x3", ptr(x.F.contiguous()), ptr(x.absmax()), Cin,
-                     ptr(tile_union(in_cs, out_cs, kernel_size, in_cs.stride)), ptr(split_weights_f16_frag(weight)), Cout,
-                     ptr(scale), ptr(shift), ptr(res), ACT[act], ptr(out), ptr(out_amax), out_cs.n, ptr(out_cs.n_dev),
-                     ptr(go_ws), go_ws_bytes, ptr(counters), stream())
-                return SparseTensor(out, out_cs, None, out_amax)
-            call("cnrma_sparse_conv_f16x3", ptr(x.F.contiguous()), ptr(x.absmax()), Cin, ptr(nbr), K,
-                 ptr(split_weights_f16(weight)), Cout, ptr(scale), ptr(shift), ptr(res), ACT[act], ptr(out), ptr(out_amax),
-                 out_cs.n, ptr(out_cs.n_dev), ptr(ws), ws_bytes, stream())
-            return SparseTensor(out, out_cs, None, out_amax)
-        if prec == "bf16x6" and Cin % 32 == 0:
-            # pre-split companions (PRESPLIT): measured on MI355X at the ScanNet shape they do not pay -- the kernel is
-            # bound by L2->LDS gather traffic, not by the in-loop split (5.6 ms either way) -- so they are off by default
-            in_split = x.split() if (PRESPLIT or x._split is not None) else None
-            if PRESPLIT and Cout % 8 == 0:
-                out_split = torch.empty((out_cs.n + 1, Cout // 8, 3, 8), dtype=torch.bfloat16, device=x.device)
-            call("cnrma_sparse_conv_bf16x6", ptr(x.F.contiguous()), ptr(in_split), x.cs.n, Cin, ptr(nbr), K, ptr(split_weights(weight)),
-                 Cout, ptr(scale), ptr(shift), ptr(res), ACT[act], ptr(out), ptr(out_split), out_cs.n, ptr(out_cs.n_dev), ptr(ws),
-                 ws_bytes, stream())
-        elif prec == "f32" and PAIR_CONV and stride == 2 and K == 27 and Cout % 4 == 0 and Cin % 32 == 0 and \
-                Cin >= PAIR_CONV_MIN_CIN and _nearly_empty_map(in_cs, out_cs):
-            # pair-list kernel in exact fp32 (the stem of the 256-channel configuration)
-            pair_cap = (min(27 * out_cs.n, 8 * in_cs.n) + 128 * K + 127) // 128 * 128
-            pw_bytes = _lib.load().cnrma_sparse_conv_pairs_workspace_bytes(out_cs.n, K, Cout, pair_cap)
-            pw = _workspace(pw_bytes, x.device)
-            call("cnrma_sparse_conv_pairs_f32", ptr(x.F.contiguous()), Cin, ptr(nbr), K, ptr(w), Cout, ptr(scale), ptr(shift),
-                 ptr(res), ACT[act], ptr(out), out_cs.n, ptr(out_cs.n_dev), pair_cap, ptr(pw), pw_bytes, stream())
-            if P.static():                          # as in the f16x3 branch: a dropped pair entry must never be silent
-                P.current().watch(pw[:PAIR_HDR_BYTES].view(torch.int32)[PAIR_OVERFLOW_WORD:PAIR_OVERFLOW_WORD + 1].clone(), 0, 0)
-        elif prec == "f32" and GO_F32 and K == 27 and stride == 1 and Cout >= 64 and Cin % 32 == 0 and _gather_once(in_cs, out_cs):
-            # exact fp32 on the gather-once structure (v_mfma_f32_32x32x2_f32 over the tile unions)
-            go_ws_bytes = out_cs.n * Cout * 4 * (Cin // 32) if out_cs.n < GO_WS_ROWS else 0
-            go_ws = _workspace(go_ws_bytes, x.device) if go_ws_bytes else None
-            call("cnrma_sparse_conv_go_f32", ptr(x.F.contiguous()), Cin, ptr(tile_union(in_cs, out_cs, kernel_size, in_cs.stride)),
-                 ptr(weights_f32_frag(weight)), Cout, ptr(scale), ptr(shift), ptr(res), ACT[act], ptr(out), out_cs.n,
-                 ptr(out_cs.n_dev), ptr(go_ws), go_ws_bytes, stream())
+                family = "pairs"
+            elif K == 27 and stride == 1 and Cout >= 64 and (prec == "f16x3" or GO_F32) and _gather_once(in_cs, out_cs):
+                family = "gather-once"
+        epi = (ptr(scale), ptr(shift), ptr(res), ACT[act])
+        if family == "pairs":
+            _pairs(prec, x, out_cs, nbr, weight, w, out, epi, out_amax)
+        elif family == "gather-once":
+            _gather_once_launch(prec, x.F, (in_cs, out_cs, kernel_size), Cin, out, weight=weight, absmax=x.absmax, epi=epi,
+                                out_amax=out_amax)
         else:
-            call("cnrma_sparse_conv_f32", ptr(x.F.contiguous()), Cin, ptr(nbr), K, ptr(w), Cout, ptr(scale), ptr(shift),
-                 ptr(res), ACT[act], ptr(out), out_cs.n, ptr(out_cs.n_dev), ptr(ws), ws_bytes, stream())
-    return SparseTensor(out, out_cs, out_split)
+            in_split = None
+            if prec == "bf16x6":
+                # pre-split companions (PRESPLIT): measured on MI355X at the ScanNet shape they do not pay -- the kernel is
+                # bound by L2->LDS gather traffic, not by the in-loop split (5.6 ms either way) -- so they are off by default
+                in_split = x.split() if (PRESPLIT or x._split is not None) else None
+                if PRESPLIT and Cout % 8 == 0:
+                    out_split = torch.empty((out_cs.n + 1, Cout // 8, 3, 8), dtype=torch.bfloat16, device=x.device)
+            amax = x.absmax() if prec == "f16x3" else None
+            image = w if prec == "f32" else _STAGE_IMAGE[prec](weight)
+            _stage(prec, x.F.contiguous(), amax, Cin, nbr, K, image, Cout, out, out_cs.n_dev, ws, ws_bytes, epi, out_amax,
+                   in_split, x.cs.n, out_split)
+    return SparseTensor(out, out_cs, out_split, out_amax)
+
+
+_NO_EPILOGUE = (None, None, None, 0)      # (scale, shift, residual, activation) of a plain convolution
+
+
+def _stage(prec, feats, amax, Cin, nbr, K, image, Cout, out, n_dev, ws, ws_bytes, epi=_NO_EPILOGUE, out_amax=None,
+           in_split=None, in_zero_row=0, out_split=None):
+    """the stage kernel (cnrma_sparse_conv_<prec>) over any neighbour table: out [n, Cout]; `image` = the prepared weights of
+    `prec` (fp32: the weight tensor itself), `amax` = the bound of |feats| (f16x3), in_split / out_split: bf16x6 companions"""
+    F, n = ptr(feats), out.shape[0]
+    if prec == "bf16":
+        call("cnrma_sparse_conv_bf16", F, Cin, ptr(nbr), K, ptr(image), Cout, *epi, ptr(out), n, ptr(n_dev), ptr(ws), ws_bytes,
+             stream())
+    elif prec == "f16x3":
+        call("cnrma_sparse_conv_f16x3", F, ptr(amax), Cin, ptr(nbr), K, ptr(image), Cout, *epi, ptr(out), ptr(out_amax), n,
+             ptr(n_dev), ptr(ws), ws_bytes, stream())
+    elif prec == "bf16x6":
+        call("cnrma_sparse_conv_bf16x6", F, ptr(in_split), in_zero_row, Cin, ptr(nbr), K, ptr(image), Cout, *epi, ptr(out),
+             ptr(out_split), n, ptr(n_dev), ptr(ws), ws_bytes, stream())
+    else:
+        call("cnrma_sparse_conv_f32", F, Cin, ptr(nbr), K, ptr(image), Cout, *epi, ptr(out), n, ptr(n_dev), ptr(ws), ws_bytes,
+             stream())
+
+
+def _pairs(prec, x, out_cs, nbr, weight, w, out, epi, out_amax):
+    """pair-list kernel (f16x3 or exact fp32): the kernel map of a stride-2 convolution on a point sample is ~5 % full"""
+    K, Cin, Cout = w.shape
+    pair_cap = (min(27 * out_cs.n, 8 * x.cs.n) + 128 * K + 127) // 128 * 128
+    pw_bytes = _lib.load().cnrma_sparse_conv_pairs_workspace_bytes(out_cs.n, K, Cout, pair_cap)
+    pw = _workspace(pw_bytes, x.device)
+    if prec == "f16x3":
+        call("cnrma_sparse_conv_pairs_f16x3", ptr(x.F.contiguous()), ptr(x.absmax()), Cin, ptr(nbr), K,
+             ptr(split_weights_f16(weight)), Cout, *epi, ptr(out), ptr(out_amax), out_cs.n, ptr(out_cs.n_dev), pair_cap, ptr(pw),
+             pw_bytes, stream())
+    else:
+        call("cnrma_sparse_conv_pairs_f32", ptr(x.F.contiguous()), Cin, ptr(nbr), K, ptr(w), Cout, *epi, ptr(out), out_cs.n,
+             ptr(out_cs.n_dev), pair_cap, ptr(pw), pw_bytes, stream())
+    if P.static():
+        # the kernels flag pair entries dropped for want of capacity in word 98 of the workspace header (the capacity above
+        # is the provable bound, so this never fires; a violated assumption must still never be silent: the word joins the
+        # plan's status -- copied out, the workspace is reused by the next layer)
+        P.current().watch(pw[:PAIR_HDR_BYTES].view(torch.int32)[PAIR_OVERFLOW_WORD:PAIR_OVERFLOW_WORD + 1].clone(), 0, 0)
+
+
+def _go_ws_bytes(n, Cin, Cout):
+    """workspace of a gather-once launch: room for the split over channel slices of a short layer (the kernel decides)"""
+    return n * Cout * 4 * (Cin // 32) if n < GO_WS_ROWS else 0
+
+
+def _gather_once_launch(prec, feats, sets, Cin, out, weight=None, image=None, absmax=None, epi=_NO_EPILOGUE, out_amax=None):
+    """gather-once kernel (3x3x3, same coordinates): a tile's distinct input rows staged once per channel slice, the offsets run
+    from LDS.  f16x3 / f32: the image is prepared from `weight`; "bf16" (training): `image` is given, no epilogue and no live
+    count.  absmax: the bound of |feats| (f16x3), asked for after the workspace is taken"""
+    in_cs, out_cs, ksize = sets
+    n, Cout = out.shape
+    go_ws_bytes = _go_ws_bytes(n, Cin, Cout)
+    go_ws = _workspace(go_ws_bytes, out.device) if go_ws_bytes else None
+    F = ptr(feats.contiguous().float())
+    if prec == "f16x3":
+        counters = _tile_counters(out.device) if GO_INKERNEL_REDUCE and go_ws_bytes and \
+            -(-n // 64) * -(-Cout // 64) <= _COUNTER_WORDS else GO_STAMPS
+        call("cnrma_sparse_conv_go_f16x3", F, ptr(absmax()), Cin, ptr(tile_union(in_cs, out_cs, ksize, in_cs.stride)),
+             ptr(split_weights_f16_frag(weight)), Cout, *epi, ptr(out), ptr(out_amax), n, ptr(out_cs.n_dev), ptr(go_ws),
+             go_ws_bytes, ptr(counters), stream())
+    elif prec == "f32":
+        call("cnrma_sparse_conv_go_f32", F, Cin, ptr(tile_union(in_cs, out_cs, ksize, in_cs.stride)), ptr(weights_f32_frag(weight)),
+             Cout, *epi, ptr(out), n, ptr(out_cs.n_dev), ptr(go_ws), go_ws_bytes, stream())
+    else:
+        call("cnrma_sparse_conv_go_bf16", F, Cin, ptr(tile_union(in_cs, out_cs, ksize, in_cs.stride)), ptr(image), Cout, ptr(out),
+             n, None, ptr(go_ws), go_ws_bytes, stream())
 
 
 TRAIN_GO = "auto"       # bf16 training: forward and data gradient of the same-coordinates 3x3x3 convolutions on the gather-once
@@ -917,13 +925,8 @@ def _train_go(sets, n_out, Cin, Cout):
 
 
 def _conv_go_bf16(feats, sets, image, Cin, Cout):
-    in_cs, out_cs, ksize = sets
-    n = out_cs.n
-    out = torch.empty((n, Cout), dtype=torch.float32, device=feats.device)
-    go_ws_bytes = n * Cout * 4 * (Cin // 32) if n < GO_WS_ROWS else 0
-    go_ws = _workspace(go_ws_bytes, feats.device) if go_ws_bytes else None
-    call("cnrma_sparse_conv_go_bf16", ptr(feats.contiguous().float()), Cin, ptr(tile_union(in_cs, out_cs, ksize, in_cs.stride)),
-         ptr(image), Cout, ptr(out), n, None, ptr(go_ws), go_ws_bytes, stream())
+    out = torch.empty((sets[1].n, Cout), dtype=torch.float32, device=feats.device)
+    _gather_once_launch("bf16", feats, sets, Cin, out, image=image)
     return out
 
 
@@ -946,36 +949,30 @@ def _conv_on_table(feats, n_out, nbr, weight, precision=None, bf16_image=None):
     if bf16_image is not None:
         (K, Cin, Cout), image = bf16_image
         assert _precision(precision) == "bf16" and Cin % 32 == 0
-        out = torch.empty((n_out, Cout), dtype=torch.float32, device=feats.device)
-        if n_out == 0:
-            return out
-        ws_bytes = _lib.load().cnrma_sparse_conv_workspace_bytes(n_out, Cout, K)
-        ws = _workspace(ws_bytes, feats.device) if ws_bytes else None
-        call("cnrma_sparse_conv_bf16", ptr(feats.contiguous().float()), Cin, ptr(nbr), K, ptr(image), Cout,
-             None, None, None, 0, ptr(out), n_out, None, ptr(ws), ws_bytes, stream())
-        return out
-    w = weight.detach().contiguous().float()
-    if w.dim() == 2:
-        w = w.unsqueeze(0)
-    K, Cin, Cout = w.shape
+    else:
+        w = weight.detach().contiguous().float()
+        if w.dim() == 2:
+            w = w.unsqueeze(0)
+        K, Cin, Cout = w.shape
     out = torch.empty((n_out, Cout), dtype=torch.float32, device=feats.device)
     if n_out == 0:
         return out
     ws_bytes = _lib.load().cnrma_sparse_conv_workspace_bytes(n_out, Cout, K)
     ws = _workspace(ws_bytes, feats.device) if ws_bytes else None
     feats = feats.contiguous().float()
-    prec = _precision(precision)
-    if prec == "bf16" and Cin % 32 == 0:
-        call("cnrma_sparse_conv_bf16", ptr(feats), Cin, ptr(nbr), K, ptr(weights_bf16(weight)), Cout,
-             None, None, None, 0, ptr(out), n_out, None, ptr(ws), ws_bytes, stream())
-    elif prec == "f16x3" and Cin % 32 == 0:
+    prec = _precision(precision) if Cin % 32 == 0 else "f32"
+    amax = None
+    if bf16_image is not None:
+        prec = "bf16"
+    elif prec == "f16x3":
         amax = torch.zeros(_AMAX_WORDS, dtype=torch.float32, device=feats.device)
         call("cnrma_absmax_f32", ptr(feats), feats.shape[0], None, Cin, ptr(amax), stream())
-        call("cnrma_sparse_conv_f16x3", ptr(feats), ptr(amax), Cin, ptr(nbr), K, ptr(split_weights_f16(weight)), Cout, None, None,
-             None, 0, ptr(out), None, n_out, None, ptr(ws), ws_bytes, stream())
+        image = split_weights_f16(weight)
+    elif prec == "bf16":
+        image = weights_bf16(weight)
     else:
-        call("cnrma_sparse_conv_f32", ptr(feats), Cin, ptr(nbr), K, ptr(w), Cout, None, None, None, 0, ptr(out), n_out, None,
-             ptr(ws), ws_bytes, stream())
+        prec, image = "f32", w
+    _stage(prec, feats, amax, Cin, nbr, K, image, Cout, out, None, ws, ws_bytes)
     return out
 
 
