@@ -144,6 +144,14 @@ __device__ __forceinline__ int64_t hash_find(const uint64_t* keys, int64_t cap, 
   return -1;
 }
 
+// probe of the site (x, y, z) = a stored coordinate + a kernel offset.  coord_key() keeps 16 bits per axis, so a site outside
+// [-32768, 32767] would wrap to the key of the voxel 65536 sites away (a stride-4 level legally holds -32768 and 32764, and
+// 32764 + 4 wraps to -32768): no voxel can live there (the voxeliser admits |x| < 32767), so such a probe finds nothing
+__device__ __forceinline__ int64_t hash_find_site(const uint64_t* keys, int64_t cap, int b, int x, int y, int z) {
+  const bool in_range = (unsigned)(x + 32768) < 65536u && (unsigned)(y + 32768) < 65536u && (unsigned)(z + 32768) < 65536u;
+  return in_range ? hash_find(keys, cap, coord_key(b, x, y, z)) : -1;
+}
+
 // insert key; returns its slot (claims an empty slot with CAS when absent)
 __device__ __forceinline__ int64_t hash_insert(uint64_t* keys, int64_t cap, uint64_t key) {
   int64_t slot = hash_u64(key) & (cap - 1);

@@ -277,7 +277,7 @@ __global__ __launch_bounds__(256) void kernel_map_kernel(const int32_t* __restri
   const int64_t o = t / K;
   const int k = (int)(t - o * K);
   int4 c = reinterpret_cast<const int4*>(out_coords)[o];
-  int64_t s = hash_find(keys, cap, coord_key(c.x, c.y + offsets[k * 3], c.z + offsets[k * 3 + 1], c.w + offsets[k * 3 + 2]));
+  int64_t s = hash_find_site(keys, cap, c.x, c.y + offsets[k * 3], c.z + offsets[k * 3 + 1], c.w + offsets[k * 3 + 2]);
   nbr[t] = s >= 0 ? vals[s] : -1;
 }
 
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void kernel_map_symmetric_kernel(const int32_t
   const int k = (int)(t - o * (half + 1));
   if (k == half) { nbr[o * K + half] = (int32_t)o; return; }
   int4 c = reinterpret_cast<const int4*>(coords)[o];
-  int64_t s = hash_find(keys, cap, coord_key(c.x, c.y + offsets[k * 3], c.z + offsets[k * 3 + 1], c.w + offsets[k * 3 + 2]));
+  int64_t s = hash_find_site(keys, cap, c.x, c.y + offsets[k * 3], c.z + offsets[k * 3 + 1], c.w + offsets[k * 3 + 2]);
   if (s >= 0) {
     const int32_t i = vals[s];
     if (i >= 0) {                      // < 0: a row dropped by its producer (over the planned capacity)
@@ -343,7 +343,7 @@ __global__ __launch_bounds__(256) void kernel_map_strided_kernel(const int32_t* 
       for (int d = 0; d < nz; ++d) {
         const int offx = ox ? (a == 0 ? 1 : -1) : 0, offy = oy ? (b == 0 ? 1 : -1) : 0, offz = oz ? (d == 0 ? 1 : -1) : 0;
         const int qx = c.y - offx * s, qy = c.z - offy * s, qz = c.w - offz * s;
-        const int64_t slot = hash_find(out_keys, cap, coord_key(c.x, qx, qy, qz));
+        const int64_t slot = hash_find_site(out_keys, cap, c.x, qx, qy, qz);
         if (slot >= 0 && out_vals[slot] >= 0)
           nbr[(int64_t)out_vals[slot] * 27 + ((offx + 1) + 3 * (offy + 1) + 9 * (offz + 1))] = (int32_t)i;
       }
@@ -3077,7 +3077,7 @@ __global__ __launch_bounds__(256) void interp_kernel(const int32_t* __restrict__
     const float w = (1.0f - fabsf((float)(q.y - cx)) / fs) * (1.0f - fabsf((float)(q.z - cy)) / fs) *
                     (1.0f - fabsf((float)(q.w - cz)) / fs);
     if (w == 0.0f) continue;
-    int64_t slot = hash_find(keys, cap, coord_key(q.x, cx, cy, cz));
+    int64_t slot = hash_find_site(keys, cap, q.x, cx, cy, cz);
     if (slot >= 0 && vals[slot] >= 0) acc += w * score[vals[slot]];
   }
   out[i] = acc;

@@ -125,3 +125,51 @@ def edge_facts(g):
             r = torch.nonzero(hit)[:, 0]
             f["depth_before_entry"] += int((~valid[r, best[r]] & valid[r, best[r] + 1]).sum())
     return f
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sparse tensors whose capacity exceeds their live row count (tests/test_sparse_edges_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+POISON = 3e38           # a dead feature / residual value: finite, safe to read, and 3e38 * anything visible in any sum or maximum
+
+
+def poison_coords(c, cap, step=1):
+    """coordinates [cap, 4] whose rows >= len(c) are poison: copies of the live rows shifted by one voxel of the lattice
+    (`step`) along x -- in range, duplicates of one another and neighbours of live rows, so a builder that reads one of them
+    makes a duplicate or a false neighbour.  A shift that would leave +-32767 goes the other way."""
+    c = np.asarray(c, dtype=np.int64)
+    live = len(c)
+    out = np.zeros((cap, 4), dtype=np.int64)
+    out[:live] = c
+    if live and cap > live:
+        dead = c[np.arange(cap - live) % live].copy()
+        dead[:, 1] += np.where(dead[:, 1] + step > 32766, -step, step)
+        out[live:] = dead
+    return out
+
+
+def poison_rows(a, cap, device, value=POISON):
+    """device tensor [cap, C]: the rows of `a` followed by rows of `value` (built on the device: capacities reach 250 000)"""
+    a = torch.as_tensor(a, dtype=torch.float32)
+    out = torch.full((cap, a.shape[1]), value, dtype=torch.float32, device=device)
+    out[:a.shape[0]] = a.to(device)
+    return out
+
+
+def capacity_tensor(c, f, ts, device, cap=None, value=POISON, n_batch=None, compact=False):
+    """SparseTensor of the rows (c, f) at tensor stride ts.  cap None / == len(c): an exact-size set (no live word, what the eager
+    wrappers build); cap > len(c): CoordSet(n=cap, n_dev=live word) with poisoned coordinates and features behind the live
+    rows -- what a static trace hands every kernel"""
+    from cnrma_amd import sparse as S
+    live = len(c)
+    nb = int(n_batch if n_batch is not None else (np.asarray(c)[:, 0].max() + 1 if live else 1))
+    if cap is None or cap == live:
+        cs = S.CoordSet(torch.from_numpy(np.asarray(c).astype(np.int32)).to(device), ts, n_batch=nb)
+        F = torch.as_tensor(f, dtype=torch.float32).to(device)
+    else:
+        assert cap > live
+        n_dev = torch.tensor([live], dtype=torch.int32, device=device)
+        cs = S.CoordSet(torch.from_numpy(poison_coords(c, cap, ts).astype(np.int32)).to(device), ts, n_batch=nb, n=cap, n_dev=n_dev)
+        F = poison_rows(f, cap, device, value)
+    cs.compact = compact
+    return S.SparseTensor(F, cs)
