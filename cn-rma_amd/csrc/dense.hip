@@ -39,7 +39,8 @@ __device__ __forceinline__ void voxel_world(const DenseParams& p, int64_t g, flo
 // group owns (chunks c, c + 8, ... as before), so the ~8 bricks an XCD has in flight are compact 0.64 x 0.64 x 1.28 m
 // boxes in which a ray meets several of its voxels.  Measured at the north-star shape (scripts/dense_ab.py, results
 // bit-identical): 13.3 -> 10.7 ms; 64 x 64 x 16 slabs 12.8, 32 x 32 x 16 11.5, 16 x 16 x 64 10.8, 8 x 8 x 32 11.5,
-// 128 x 128 x 16 19.0 ms.  Stores stay 32-byte runs along z per lane group, merged in L2 (zt >= 16).
+// 128 x 128 x 16 19.0 ms.  A lane of the product kernel stores runs of 4 consecutive z (group_src_lane() below): whole 128-byte
+// lines per store instruction where zi % 4 == 0 and the grid allows it.
 struct SlabOrder { int on, nsx, nsy, nsz, zt, st, tt, zi, nt, own, stagger, groups; };  // zt: z-layers per brick, st: brick side, tt: tile side (columns), zi: inner z run
 
 __device__ __forceinline__ bool slab_decode(const DenseParams& p, const SlabOrder& o, int64_t gv, int* x, int* y, int* z) {
@@ -139,9 +140,9 @@ __global__ __launch_bounds__(256) void backproject_accum_kernel(DenseParams p, c
 }
 
 // ---- pipelined cooperative-gather kernel (round 3; the product kernel) ------------------------------------------------
-// Same lane <-> voxel / channel mapping and the same arithmetic as backproject_accum_coop_kernel (results bit-identical),
-// but built for memory-level parallelism.  The round-2 loop put every gather inside its own conditional block, and the
-// compiler closed each with `s_waitcnt vmcnt(0)`: ONE 1-KB gather in flight per wave, 24 KB per CU -- the kernel was bound
+// The same arithmetic as backproject_accum_coop_kernel (results bit-identical; which lane gathers and stores for which voxel
+// of the wave is group_src_lane()'s choice), but built for memory-level parallelism.  The round-2 loop put every gather
+// inside its own conditional block, and the compiler closed each with `s_waitcnt vmcnt(0)`: ONE 1-KB gather in flight per wave, 24 KB per CU -- the kernel was bound
 // by the latency of a single L2 / Infinity-Cache / HBM round trip (its run time scaled 1:1 with the number of resident
 // waves), not by bandwidth.  Here all LPV gathers of a view are issued back to back (exec-masked loads,
 // no branch in between), the projection of the NEXT view is computed while they fly, and only then are they added; with
@@ -171,6 +172,32 @@ __device__ __forceinline__ void group_barrier(unsigned int* w, unsigned int n) {
   __syncthreads();
 }
 
+// Which lane's voxel a lane accumulates as its group `grp` (lane = vsel * LPV + sub; the LPV lanes of one vsel read one pixel
+// line together).  Any bijection works for the gathers: an instruction touches 64 / LPV pixel lines either way.
+//   EPI == 0, LPV >= 4 (product): runs of 4 consecutive lanes -- lane (sub, vsel) owns voxels vsel*4 .. vsel*4+3 of every block of
+//   4*VPG lanes, i.e. 4 consecutive z of one column, so its four accumulators of a channel are four consecutive floats of a
+//   [C][X][Y][Z] plane and leave as ONE 16-byte store: a store instruction writes 16 * VPG contiguous bytes in each of LPV planes
+//   (8 whole 128-byte lines at LPV = 8).
+//   otherwise: voxel grp*VPG + vsel (a store instruction writes 4 * VPG bytes in each of LPV planes: 32-byte pieces at LPV = 8;
+//   EPI == 2 keeps this form selectable for A/B runs in the experiments library).
+template <int LPV, int EPI>
+__device__ __forceinline__ int group_src_lane(int grp, int vsel) {
+  constexpr int VPG = 64 / LPV;
+  if constexpr (EPI == 0 && LPV >= 4) return (grp / 4) * (4 * VPG) + vsel * 4 + (grp % 4);
+  else return grp * VPG + vsel;
+}
+
+typedef float dense_f4 __attribute__((ext_vector_type(4)));
+
+// one 16-byte store of a z-run.  policy 0: plain, 1: non-temporal, 2: sc1 (write-through: the line is not kept in the XCD's L2)
+__device__ __forceinline__ void store_run(float* o, float a, float b, float c, float d, int policy) {
+  dense_f4 v = {a, b, c, d};
+  if (policy == 1) __builtin_nontemporal_store(v, reinterpret_cast<dense_f4*>(o));
+  else if (policy == 2) asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(o), "v"(v) : "memory");
+  else *reinterpret_cast<dense_f4*>(o) = v;
+}
+
+// EPI: 0 direct stores, z-run lane mapping (16-byte stores)   1 LDS-transposed stores   2 direct stores, round-3 lane mapping
 template <int LPV, int PIPE, int EPI>
 __device__ __forceinline__ void accum_block(const DenseParams& p, const float* __restrict__ feat,
                                             const float* __restrict__ proj, float* __restrict__ volume,
@@ -212,7 +239,7 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     const float* fv = fbase + v * plane;
 #pragma unroll
     for (int grp = 0; grp < LPV; ++grp) {
-      const int pq = __shfl(pix, grp * VPG + vsel, 64);
+      const int pq = __shfl(pix, group_src_lane<LPV, EPI>(grp, vsel), 64);
       q[grp] = make_float4(0.f, 0.f, 0.f, 0.f);
       if (pq >= 0) q[grp] = *reinterpret_cast<const float4*>(fv + (int64_t)pq * p.C);
     }
@@ -257,12 +284,49 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     }
   }
 
-  // means.  The count of the voxel a lane accumulates for (group grp) lives in lane grp*VPG + vsel.
-  if constexpr (EPI == 0) {
+  // means.  The count and the linear index of the voxel a lane accumulates for (group grp) live in lane group_src_lane(grp).
+  if constexpr (EPI == 0 && LPV >= 4) {
+    // z-run mapping: groups 4r .. 4r+3 of a lane are 4 consecutive lanes' voxels.  A run leaves as one 16-byte store per channel
+    // when its four voxels are in the grid at consecutive linear indices starting at a multiple of 4, with G % 4 == 0 and a
+    // 16-byte aligned volume (then every plane's run is 16-byte aligned); otherwise (ragged bricks, Z % 4 != 0, odd grids,
+    // offset output views) that run is stored element by element.  Decided per run; all shuffles are outside the branches.
+    const bool vec_ok = (G & 3) == 0 && (reinterpret_cast<uintptr_t>(volume) & 15) == 0;
+    const int c = c0 + 4 * sub;
+#pragma unroll
+    for (int r = 0; r < LPV / 4; ++r) {
+      int64_t gv[4];
+      float m[4][4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int src = group_src_lane<LPV, EPI>(4 * r + k, vsel);
+        const int cv = __shfl(cnt, src, 64);
+        const int lo = __shfl((int)(lin & 0xffffffffLL), src, 64), hi = __shfl((int)(lin >> 32), src, 64);
+        gv[k] = ((int64_t)hi << 32) | (uint32_t)lo;
+        const float denom = (float)cv;
+        const float4 a = acc[4 * r + k];
+        m[k][0] = cv > 0 ? a.x / denom : 0.0f; m[k][1] = cv > 0 ? a.y / denom : 0.0f;
+        m[k][2] = cv > 0 ? a.z / denom : 0.0f; m[k][3] = cv > 0 ? a.w / denom : 0.0f;
+      }
+      const bool whole = vec_ok && gv[0] >= 0 && (gv[0] & 3) == 0 && gv[1] == gv[0] + 1 && gv[2] == gv[0] + 2 && gv[3] == gv[0] + 3;
+      if (whole) {
+        float* o = volume + (int64_t)c * G + gv[0];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) store_run(o + j * G, m[0][j], m[1][j], m[2][j], m[3][j], ord.nt);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (gv[k] >= 0) {
+            float* o = volume + (int64_t)c * G + gv[k];
+            o[0] = m[k][0]; o[G] = m[k][1]; o[2 * G] = m[k][2]; o[3 * G] = m[k][3];
+          }
+      }
+    }
+  } else if constexpr (EPI != 1) {
 #pragma unroll
     for (int grp = 0; grp < LPV; ++grp) {
-      const int cv = __shfl(cnt, grp * VPG + vsel, 64);
-      const int lo = __shfl((int)(lin & 0xffffffffLL), grp * VPG + vsel, 64), hi = __shfl((int)(lin >> 32), grp * VPG + vsel, 64);
+      const int src = group_src_lane<LPV, EPI>(grp, vsel);
+      const int cv = __shfl(cnt, src, 64);
+      const int lo = __shfl((int)(lin & 0xffffffffLL), src, 64), hi = __shfl((int)(lin >> 32), src, 64);
       const int64_t gv = ((int64_t)hi << 32) | (uint32_t)lo;
       if (gv >= 0) {
         const float denom = (float)cv;
@@ -271,7 +335,7 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
         const float m0 = cv > 0 ? a.x / denom : 0.0f, m1 = cv > 0 ? a.y / denom : 0.0f, m2 = cv > 0 ? a.z / denom : 0.0f,
                     m3 = cv > 0 ? a.w / denom : 0.0f;
         float* o = volume + (int64_t)c * G + gv;
-        if (ord.nt) {                           // streaming stores: the volume is written once and not read here
+        if (ord.nt == 1) {                      // streaming stores: the volume is written once and not read here
           __builtin_nontemporal_store(m0, o); __builtin_nontemporal_store(m1, o + G);
           __builtin_nontemporal_store(m2, o + 2 * G); __builtin_nontemporal_store(m3, o + 3 * G);
         } else { o[0] = m0; o[G] = m1; o[2 * G] = m2; o[3 * G] = m3; }
@@ -320,8 +384,8 @@ __global__ __launch_bounds__(256, PIPE == 1 ? 4 : 3) void backproject_accum_pipe
   // feat_ref != NULL: the feature maps are handed over BY REFERENCE -- a device word holds their address (one scalar load);
   // a captured launch sequence can then read whatever tensor the producer wrote, with no copy into a static buffer
   if (feat_ref != nullptr) feat = *feat_ref;
-  __shared__ float lds[EPI ? 4 * (4 * LPV) * 65 : 1];
-  float* lds_wave = lds + (EPI ? (threadIdx.x >> 6) * (4 * LPV) * 65 : 0);
+  __shared__ float lds[EPI == 1 ? 4 * (4 * LPV) * 65 : 1];
+  float* lds_wave = lds + (EPI == 1 ? (threadIdx.x >> 6) * (4 * LPV) * 65 : 0);
   if constexpr (LOCK != 0) {
     // persistent grid: gridDim.x = 8 * chunk_blocks; group = blockIdx.x & 7 walks chunks group, group + 8, ...; all channel
     // sweeps inside (blockIdx.y unused)
@@ -377,13 +441,14 @@ struct DenseTune {
   int lpv = 0;          // 0: by channel count; 4 / 8 / 16 / 32 lanes (x 4 channels) per voxel
   int pipe = 1;         // variant 1: views in flight (1 | 2)
   int epi = 0;          // variant 1: 0 direct stores, 1 LDS-transposed full-line stores
-  int nt = 0;           // variant 1: non-temporal stores of the volume
+  int nt = 0;           // variant 1: cache policy of the volume stores: 0 plain, 1 non-temporal, 2 sc1 (write-through; 16-byte stores only)
   int own = 0;          // variant 1: one channel sweep per XCD group (needs exactly 8 sweeps)
   int stagger = 0;      // variant 1 lockstep: start delay per wave index, in units of 64 cycles
   int ldspad = 0;       // variant 1: KB of unused dynamic LDS per workgroup (caps the workgroups per CU: leaves room for co-resident kernels)
   int groups = 8;       // variant 1 lockstep: 8 = one brick per XCD at a time, 16 = two independent half-size groups per XCD
   int lattice = 0;      // variant 1 lockstep: 1 = lattice assignment of columns to workgroups (balanced), 0 = compact tiles
   int lockstep = 0;     // variants 1, 2: persistent grid, every XCD group walks one brick at a time (1: behind a barrier, 2: no barrier)
+  int zrun = 1;         // variant 1, epi 0: 1 = a lane owns runs of 4 consecutive z (16-byte stores), 0 = the round-3 lane mapping (4-byte stores)
 };
 #ifdef CNRMA_EXPERIMENTS
 static DenseTune g_tune;                     // libcnrma_hip_exp.so only: written by cnrma_debug_dense_tuning
@@ -454,10 +519,10 @@ int launch_accum_coop(const DenseParams& p, const float* feat, const float* proj
       hipLaunchKernelGGL((backproject_accum_pipe_kernel<LPV, PIPE, EPI, 0>), grid, dim3(256), (size_t)t.ldspad * 1024, st, p,  \
                          feat, proj, volume, count, (int)cb, gx, ord, bar, feat_ref);                                     \
   } while (0)
-  if (t.pipe == 2) { if (t.epi) CNRMA_DENSE_LAUNCH(2, 1); else CNRMA_DENSE_LAUNCH(2, 0); }
-  else             { if (t.epi) CNRMA_DENSE_LAUNCH(1, 1); else CNRMA_DENSE_LAUNCH(1, 0); }
+  if (t.pipe == 2) { if (t.epi) CNRMA_DENSE_LAUNCH(2, 1); else if (t.zrun) CNRMA_DENSE_LAUNCH(2, 0); else CNRMA_DENSE_LAUNCH(2, 2); }
+  else             { if (t.epi) CNRMA_DENSE_LAUNCH(1, 1); else if (t.zrun) CNRMA_DENSE_LAUNCH(1, 0); else CNRMA_DENSE_LAUNCH(1, 2); }
 #undef CNRMA_DENSE_LAUNCH
-#else                                   // the product schedule: one view in flight per wave, direct stores, free-running grid
+#else                                   // the product schedule: one view in flight per wave, direct 16-byte stores of z-runs, free-running grid
   (void)lock;
   hipLaunchKernelGGL((backproject_accum_pipe_kernel<LPV, 1, 0, 0>), grid, dim3(256), 0, st, p, feat, proj, volume, count, (int)cb, gx,
                      ord, bar, feat_ref);
@@ -495,11 +560,11 @@ int launch_accum(const DenseParams& p, const float* feat, const float* proj, flo
 
 #ifdef CNRMA_EXPERIMENTS
 extern "C" int cnrma_debug_dense_tuning(const int* v, int n) {
-  // v = {variant, slab, st, zt, tt, zi, chunk, persist, lpv, pipe, epi, lockstep, lattice, nt, own, stagger, groups, ldspad}; n < 18 keeps the remaining defaults;
+  // v = {variant, slab, st, zt, tt, zi, chunk, persist, lpv, pipe, epi, lockstep, lattice, nt, own, stagger, groups, ldspad, zrun}; n < 19 keeps the remaining defaults;
   // n == 0 restores the product configuration.  Host-side global state: debug / A-B runs only.
   DenseTune t;
-  int* f[] = {&t.variant, &t.slab, &t.st, &t.zt, &t.tt, &t.zi, &t.chunk, &t.persist, &t.lpv, &t.pipe, &t.epi, &t.lockstep, &t.lattice, &t.nt, &t.own, &t.stagger, &t.groups, &t.ldspad};
-  if (n < 0 || n > 18 || (n > 0 && v == nullptr)) return CNRMA_EINVAL;
+  int* f[] = {&t.variant, &t.slab, &t.st, &t.zt, &t.tt, &t.zi, &t.chunk, &t.persist, &t.lpv, &t.pipe, &t.epi, &t.lockstep, &t.lattice, &t.nt, &t.own, &t.stagger, &t.groups, &t.ldspad, &t.zrun};
+  if (n < 0 || n > 19 || (n > 0 && v == nullptr)) return CNRMA_EINVAL;
   for (int i = 0; i < n; ++i) *f[i] = v[i];
   g_tune = t;
   return 0;
@@ -513,9 +578,11 @@ static int backproject_accum_any(const float* feat_nhwc, const float* const* fea
   DenseParams p{V, C, H, W, X, Y, Z, voxel_size, ox, oy, oz};
   hipStream_t st = as_stream(stream);
   unsigned int* bar = (workspace != nullptr && workspace_bytes >= CNRMA_DENSE_WORKSPACE_BYTES) ? static_cast<unsigned int*>(workspace) : nullptr;
+#ifdef CNRMA_EXPERIMENTS                // lanes per voxel by hand: the 16-lane form exists in the experiments library only
   const int l = CNRMA_DENSE_TUNE.lpv;
   if (l == 16 && C % 64 == 0) return launch_accum_coop<16>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
   if (l == 4 && C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
+#endif
   if (C % 32 == 0) return launch_accum_coop<8>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
   if (C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
   if (C % 8 == 0) return launch_accum_coop<2>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
