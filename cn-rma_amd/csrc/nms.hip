@@ -51,13 +51,21 @@ __device__ float quad_intersection_area(const P2* A, const P2* B) {
   return fabsf(area) * 0.5f;
 }
 
+// BEV overlap of two rotated boxes.  A box without area overlaps nothing: its edges have no length or its corners no interior,
+// so every point passes the clipper's side test and the other box would come back whole.
+// Sizes are taken to be >= 0: a box with two negative sizes is outside the contract and is not caught by the product test.
+__device__ __forceinline__ float rotated_bev_intersection(const float* a, const float* b) {
+  if (!(a[3] * a[4] > 0.0f) || !(b[3] * b[4] > 0.0f)) return 0.0f;
+  P2 ca[4], cb[4];
+  bev_corners(a, ca);
+  bev_corners(b, cb);
+  return quad_intersection_area(ca, cb);
+}
+
 __device__ __forceinline__ float bev_iou(const float* a, const float* b, int rotated) {
   float inter;
   if (rotated) {
-    P2 ca[4], cb[4];
-    bev_corners(a, ca);
-    bev_corners(b, cb);
-    inter = quad_intersection_area(ca, cb);
+    inter = rotated_bev_intersection(a, b);
   } else {
     const float lx = fmaxf(a[0] - a[3] * 0.5f, b[0] - b[3] * 0.5f), rx = fminf(a[0] + a[3] * 0.5f, b[0] + b[3] * 0.5f);
     const float ly = fmaxf(a[1] - a[4] * 0.5f, b[1] - b[4] * 0.5f), ry = fminf(a[1] + a[4] * 0.5f, b[1] + b[4] * 0.5f);
@@ -101,10 +109,7 @@ __global__ __launch_bounds__(256) void iou_matrix_kernel(const float* __restrict
   if (!mode3d) { iou[t] = bev_iou(p, q, rotated); return; }
   float inter;
   if (rotated) {
-    P2 ca[4], cb[4];
-    bev_corners(p, ca);
-    bev_corners(q, cb);
-    inter = quad_intersection_area(ca, cb);
+    inter = rotated_bev_intersection(p, q);
   } else {
     const float lx = fmaxf(p[0] - p[3] * 0.5f, q[0] - q[3] * 0.5f), rx = fminf(p[0] + p[3] * 0.5f, q[0] + q[3] * 0.5f);
     const float ly = fmaxf(p[1] - p[4] * 0.5f, q[1] - q[4] * 0.5f), ry = fminf(p[1] + p[4] * 0.5f, q[1] + q[4] * 0.5f);

@@ -606,7 +606,8 @@ extern "C" int cnrma_sample_mask(const int32_t* m_dev, int64_t m_cap, int n_keep
 }
 
 // mask[0..n): ones at the min(n, k) rows with the LARGEST scores (ties by smaller index) -- the keep-set of
-// torch.topk(scores, k) without the sort; n = n_dev[0] read on the device
+// torch.topk(scores, k) without the sort; n = n_dev[0] read on the device.  "Largest" is by bit pattern (select_key: IEEE total
+// order): -0.0 ranks below +0.0, a NaN with a clear sign bit above +inf, one with a set sign bit below -inf
 extern "C" int cnrma_topk_mask_f32(const float* scores, const int32_t* n_dev, int64_t n_cap, int k, uint8_t* mask,
                                    void* workspace, void* stream) {
   if (scores == nullptr || n_dev == nullptr) return CNRMA_EINVAL;
@@ -641,7 +642,9 @@ extern "C" int cnrma_rma_select_records(const int32_t* row_offset, int64_t R, co
 }
 
 // out_idx[0..k): the rows of the k largest scores in descending score order (ties by smaller row) -- torch.topk(scores,
-// k)[1] -- for k <= 1024; with fewer than k live rows the live rows come first and the remaining slots hold row 0
+// k)[1] -- for k <= 1024; with fewer than k live rows the live rows come first and the remaining slots hold row 0.  The order is
+// that of the packed (key, row) words: by bit pattern as in cnrma_topk_mask_f32 (+0.0 before -0.0, a NaN with a clear sign bit
+// first, one with a set sign bit last), equal patterns by row
 extern "C" int cnrma_topk_indices_f32(const float* scores, const int32_t* n_dev, int64_t n_cap, int k, int64_t* out_idx,
                                       void* workspace, void* stream) {
   if (scores == nullptr || n_dev == nullptr || out_idx == nullptr || k > 1024) return CNRMA_EINVAL;

@@ -1569,7 +1569,9 @@ def select_decode(ids, cls_score, centerness, bbox_pred, points, yaw_parametriza
 
 def topk_mask(scores, k, n_dev=None):
     """uint8 keep-mask of the k largest scores (ties -> smaller index): row set of torch.topk(scores, k), no sort.
-    n_dev: device word with the live number of scores (rows behind it are never kept)."""
+    n_dev: device word with the live number of scores (rows behind it are never kept).
+    Scores rank by bit pattern (IEEE total order), not by float comparison: -0.0 ranks below +0.0, a NaN with a clear sign bit
+    above +inf and one with a set sign bit below -inf (torch.topk: +-0 equal, every NaN largest)."""
     _lib.require_gpu()
     scores = scores.contiguous().view(-1).float()
     n = scores.numel()
@@ -1599,7 +1601,10 @@ def topk_indices(scores, k, n_dev=None):
     """int64 [k] row indices of the k largest scores in descending score order (ties -> smaller index): what
     torch.topk(scores, k)[1] returns, built from the radix-select keep-mask + a compaction + a sort of only the k survivors
     (torch.topk's single-workgroup select takes 0.2-0.7 ms on ~500 k scores and sits on the critical path of a scene).
-    With fewer than k live rows (n_dev) the live rows come first, in score order; the remaining slots repeat row 0."""
+    With fewer than k live rows (n_dev) the live rows come first, in score order; the remaining slots repeat row 0.
+    The kept rows are those of topk_mask, i.e. ranked by bit pattern: for k <= 1024 they also come in that order (+0.0 before
+    -0.0, a NaN with a clear sign bit first, one with a set sign bit last, equal patterns by row); above 1024 the survivors are
+    ordered by a stable torch.sort, which agrees wherever the scores hold no NaN and no -0.0 beside a +0.0."""
     scores = scores.contiguous().view(-1).float()
     n = scores.numel()
     if 0 < k <= 1024 and n > 0:          # one select + one single-workgroup sort of the k survivors (2 + 8 launches, no torch ops)

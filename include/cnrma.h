@@ -219,12 +219,17 @@ int cnrma_rma_select_records(const int32_t* row_offset, int64_t R, const void* k
 /* keep-mask of the k largest scores (ties -> smaller index): the row set of torch.topk(scores, k) as used by the
  * pts_threshold pruning (fcaf3d_head.py:131-137) and nms_pre (:252-256), by 3-pass radix select instead of a sort.
  * n = min(n_dev[0], n_cap) (device); mask has n_cap entries, those behind n are set to 0;
- * workspace: cnrma_sample_workspace_bytes(). */
+ * workspace: cnrma_sample_workspace_bytes().
+ * ORDER: scores are ranked by BIT PATTERN (IEEE total order), not by float comparison: -0.0 ranks below +0.0, a NaN with a
+ * clear sign bit ranks above +inf and one with a set sign bit below -inf (torch.topk treats +-0 as equal and every NaN as the
+ * largest value); equal bit patterns go by the smaller row. */
 int cnrma_topk_mask_f32(const float* scores, const int32_t* n_dev, int64_t n_cap, int k, uint8_t* mask,
                         void* workspace, void* stream);
 /* torch.topk(scores, k)[1] for nms_pre (fcaf3d_head.py:252-256), k <= 1024: the same radix select, the kept rows collected
  * in a list and sorted by one workgroup -- out_idx[0..min(n, k)) = rows in descending score order (ties -> smaller row),
- * the slots behind them hold row 0.  workspace: cnrma_sample_workspace_bytes(). */
+ * the slots behind them hold row 0.  k > 1024 returns CNRMA_EINVAL.  workspace: cnrma_sample_workspace_bytes().
+ * Same order as cnrma_topk_mask_f32: by bit pattern, so -0.0 comes behind +0.0, a NaN with a clear sign bit first and one with a
+ * set sign bit last. */
 int cnrma_topk_indices_f32(const float* scores, const int32_t* n_dev, int64_t n_cap, int k, int64_t* out_idx,
                            void* workspace, void* stream);
 

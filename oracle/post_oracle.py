@@ -26,6 +26,8 @@ def _clip(poly, p, q):
 
 
 def bev_intersection(a, b):
+    if not (a[3] * a[4] > 0 and b[3] * b[4] > 0):     # a box without area overlaps nothing (the clipper would return the other box whole)
+        return 0.0
     poly = list(_corners(a))
     cb = _corners(b)
     for e in range(4):
