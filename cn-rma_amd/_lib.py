@@ -27,6 +27,8 @@ SIGNATURES = {
     "cnrma_nchw_to_nhwc_f32": (c_int, [P, P, I, I, I, I, P]),
     "cnrma_backproject_accum_f32": (c_int, [P, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
     "cnrma_backproject_accum_ref_f32": (c_int, [P, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
+    "cnrma_backproject_accum_h16": (c_int, [P, P, I, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
+    "cnrma_nchw_to_nhwc_b16": (c_int, [P, P, I, I, I, I, P]),
     "cnrma_backproject_backward_f32": (c_int, [P, P, P, I, I, I, I, I, I, I, F, F, F, F, P, P]),
     "cnrma_backproject_index_f32": (c_int, [P, I, I, I, I, I, F, F, F, F, P, P, P, P]),
     "cnrma_ray_params_f32": (c_int, [P, I, I, I, P, P, P]),
@@ -41,6 +43,7 @@ SIGNATURES = {
     "cnrma_nchw_to_nhwc_march_f32": (c_int, [P, P, I, P, P, P, I, I, I, I, I, I, F, F, F, F, I, F, F, P, P, P, I, P, P, P]),
     "cnrma_rma_neus_emit_rows_f32": (c_int, [P, P, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
     "cnrma_rma_neus_emit_rows_ref_f32": (c_int, [P, P, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
+    "cnrma_rma_neus_emit_rows_h16": (c_int, [P, P, P, I, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
     "cnrma_sample_workspace_bytes": (c_size_t, []),
     "cnrma_sample_mask": (c_int, [P, L, I, ctypes.c_uint32, P, P, P, P]),
     "cnrma_topk_mask_f32": (c_int, [P, P, L, I, P, P, P]),
@@ -76,6 +79,7 @@ SIGNATURES = {
     "cnrma_amax_bytes": (c_size_t, []),
     "cnrma_absmax_f32": (c_int, [P, L, P, I, P, P]),
     "cnrma_rma_emit_features_f32": (c_int, [P, P, I, P, L, P, P, P, I, P, P]),
+    "cnrma_rma_emit_features_h16": (c_int, [P, P, I, I, P, L, P, P, P, I, P, P]),
     "cnrma_sparse_conv_f16_weight_bytes": (c_size_t, [I, I, I]),
     "cnrma_sparse_conv_prepare_weights_f16": (c_int, [P, I, I, I, P, P]),
     "cnrma_sparse_conv_f16x3": (c_int, [P, P, I, P, I, P, I, P, P, P, I, P, P, L, P, P, c_size_t, P]),
@@ -136,7 +140,7 @@ EXPERIMENT_SIGNATURES = {
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
 _exp_users = set()    # who asked for the experiments library ("conv", "dense", a test): product again when nobody is left
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 
 class CnrmaError(RuntimeError):

@@ -85,6 +85,29 @@ __device__ __forceinline__ int64_t live_rows(int64_t cap, const int32_t* n_dev) 
   return n < cap ? n : cap;
 }
 
+// ---- 16-bit feature-map elements (ELEM: CNRMA_ELEM_F16 = IEEE half, CNRMA_ELEM_BF16 = bfloat16) -> fp32, both exact --------
+__host__ __device__ inline bool elem16_known(int elem) { return elem == CNRMA_ELEM_F16 || elem == CNRMA_ELEM_BF16; }
+
+template <int ELEM>
+__device__ __forceinline__ float elem16_to_f32(uint16_t h) {
+  if constexpr (ELEM == CNRMA_ELEM_BF16) return __uint_as_float((uint32_t)h << 16);
+  else return (float)__builtin_bit_cast(_Float16, h);
+}
+
+// the two elements of one 32-bit word of a map row (little endian: the low half is the lower channel)
+template <int ELEM>
+__device__ __forceinline__ void elem16_pair(uint32_t w, float* lo, float* hi) {
+  if constexpr (ELEM == CNRMA_ELEM_BF16) { *lo = __uint_as_float(w << 16); *hi = __uint_as_float(w & 0xffff0000u); }
+  else { *lo = elem16_to_f32<ELEM>((uint16_t)(w & 0xffffu)); *hi = elem16_to_f32<ELEM>((uint16_t)(w >> 16)); }
+}
+
+// 16 bytes = 8 consecutive channels
+template <int ELEM>
+__device__ __forceinline__ void elem16_x8(const uint4& q, float4* a, float4* b) {
+  elem16_pair<ELEM>(q.x, &a->x, &a->y); elem16_pair<ELEM>(q.y, &a->z, &a->w);
+  elem16_pair<ELEM>(q.z, &b->x, &b->y); elem16_pair<ELEM>(q.w, &b->z, &b->w);
+}
+
 // ---- wave / block scans (wave64) --------------------------------------------------------------------------
 __device__ __forceinline__ int wave_incl_scan(int v) {
 #pragma unroll

@@ -189,6 +189,11 @@ __device__ __forceinline__ int group_src_lane(int grp, int vsel) {
 
 typedef float dense_f4 __attribute__((ext_vector_type(4)));
 
+// element type of the feature maps, what one 16-byte gather holds and how many float4 accumulators (Q) it feeds
+template <int ELEM> struct DenseElem { typedef float type; typedef float4 load_t; static constexpr int Q = 1; };
+template <> struct DenseElem<CNRMA_ELEM_F16> { typedef uint16_t type; typedef uint4 load_t; static constexpr int Q = 2; };
+template <> struct DenseElem<CNRMA_ELEM_BF16> { typedef uint16_t type; typedef uint4 load_t; static constexpr int Q = 2; };
+
 // one 16-byte store of a z-run.  policy 0: plain, 1: non-temporal, 2: sc1 (write-through: the line is not kept in the XCD's L2)
 __device__ __forceinline__ void store_run(float* o, float a, float b, float c, float d, int policy) {
   dense_f4 v = {a, b, c, d};
@@ -198,12 +203,18 @@ __device__ __forceinline__ void store_run(float* o, float a, float b, float c, f
 }
 
 // EPI: 0 direct stores, z-run lane mapping (16-byte stores)   1 LDS-transposed stores   2 direct stores, round-3 lane mapping
-template <int LPV, int PIPE, int EPI>
-__device__ __forceinline__ void accum_block(const DenseParams& p, const float* __restrict__ feat,
+// ELEM: 0 fp32 maps (a lane gathers 4 channels per 16-byte load), CNRMA_ELEM_F16 / CNRMA_ELEM_BF16 16-bit maps (8 channels per
+// 16-byte load, widened exactly and summed in fp32: the same sums as on the widened maps); feat points at elements of that type
+template <int LPV, int PIPE, int EPI, int ELEM = 0>
+__device__ __forceinline__ void accum_block(const DenseParams& p, const typename DenseElem<ELEM>::type* __restrict__ feat,
                                             const float* __restrict__ proj, float* __restrict__ volume,
                                             int32_t* __restrict__ count, int64_t lb, int c0, bool write_count,
                                             const SlabOrder& ord, float* __restrict__ lds_wave, int tid) {
   constexpr int VPG = 64 / LPV;
+  constexpr int Q = DenseElem<ELEM>::Q, CPL = 4 * Q;        // float4 accumulators / channels per lane and voxel
+  typedef typename DenseElem<ELEM>::type feat_t;
+  typedef typename DenseElem<ELEM>::load_t load_t;
+  static_assert(EPI != 1 || ELEM == 0, "the LDS-transposed epilogue exists for fp32 maps only");
   const int64_t G = (int64_t)p.X * p.Y * p.Z;
   const int lane = tid & 63;
   const int64_t g = lb * 256 + tid;
@@ -222,32 +233,40 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     if (in_grid) { voxel_world(p, g, &wx, &wy, &wz); lin = g; }
   }
   if (__ballot(in_grid) == 0ull) return;
-  float4 acc[LPV];
+  float4 acc[LPV * Q];
 #pragma unroll
-  for (int i = 0; i < LPV; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int i = 0; i < LPV * Q; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
   int cnt = 0;
-  const int sub = lane % LPV, vsel = lane / LPV;
+  int sub = lane % LPV, vsel = lane / LPV;
   const int64_t plane = (int64_t)p.H * p.W * p.C;
-  const float* fbase = feat + c0 + 4 * sub;
+  const feat_t* fbase = feat + c0 + CPL * sub;
 
   auto pixel_of = [&](int v) -> int {
     float rx, ry;
     const bool ok = in_grid && project(proj + v * 12, wx, wy, wz, p.H, p.W, &rx, &ry);
     return ok ? ((int)ry * p.W + (int)rx) : -1;
   };
-  auto gather = [&](int v, int pix, float4* q) {
-    const float* fv = fbase + v * plane;
+  auto gather = [&](int v, int pix, load_t* q) {
+    const feat_t* fv = fbase + v * plane;
 #pragma unroll
     for (int grp = 0; grp < LPV; ++grp) {
       const int pq = __shfl(pix, group_src_lane<LPV, EPI>(grp, vsel), 64);
-      q[grp] = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (pq >= 0) q[grp] = *reinterpret_cast<const float4*>(fv + (int64_t)pq * p.C);
+      if constexpr (ELEM == 0) q[grp] = make_float4(0.f, 0.f, 0.f, 0.f);
+      else q[grp] = make_uint4(0u, 0u, 0u, 0u);             // +0.0 in either 16-bit type
+      if (pq >= 0) q[grp] = *reinterpret_cast<const load_t*>(fv + (int64_t)pq * p.C);
     }
   };
-  auto add = [&](const float4* q) {
+  auto add = [&](const load_t* q) {
 #pragma unroll
     for (int grp = 0; grp < LPV; ++grp) {
-      acc[grp].x += q[grp].x; acc[grp].y += q[grp].y; acc[grp].z += q[grp].z; acc[grp].w += q[grp].w;
+      if constexpr (ELEM == 0) {
+        acc[grp].x += q[grp].x; acc[grp].y += q[grp].y; acc[grp].z += q[grp].z; acc[grp].w += q[grp].w;
+      } else {
+        float4 a, b;
+        elem16_x8<ELEM>(q[grp], &a, &b);
+        acc[2 * grp].x += a.x; acc[2 * grp].y += a.y; acc[2 * grp].z += a.z; acc[2 * grp].w += a.w;
+        acc[2 * grp + 1].x += b.x; acc[2 * grp + 1].y += b.y; acc[2 * grp + 1].z += b.z; acc[2 * grp + 1].w += b.w;
+      }
     }
   };
 
@@ -256,7 +275,7 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     for (int v = 0; v < p.V; ++v) {
       const int pix = pix_n;
       const bool any = __ballot(pix >= 0) != 0ull;
-      float4 q[LPV];
+      load_t q[LPV];
       if (any) gather(v, pix, q);
       cnt += pix >= 0 ? 1 : 0;
       pix_n = (v + 1 < p.V) ? pixel_of(v + 1) : -1;        // overlaps with the gathers in flight
@@ -264,7 +283,7 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     }
   } else {
     // two views in flight: q0 holds view v (issued one iteration ago), q1 is issued for view v + 1 before q0 is consumed
-    float4 q0[LPV], q1[LPV];
+    load_t q0[LPV], q1[LPV];
     int pix0 = pixel_of(0);
     bool any0 = __ballot(pix0 >= 0) != 0ull;
     if (any0) gather(0, pix0, q0);
@@ -284,6 +303,20 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     }
   }
 
+  if constexpr (ELEM != 0 && LPV >= 8) {
+    // 64 accumulators + 32 gather registers: what the epilogue needs (the voxel's linear index, the lane's place in its group) is
+    // re-derived from a laundered thread index, so that none of it is live across the view loop
+    int t2 = tid;
+    asm volatile("" : "+v"(t2));
+    sub = (t2 & 63) % LPV; vsel = (t2 & 63) / LPV;
+    int x = 0, y = 0, z = 0;
+    const int64_t g2 = lb * 256 + t2;
+    bool in2;
+    if (ord.on) in2 = ord.on == 2 ? lattice_decode(p, ord, lb, t2, &x, &y, &z) : slab_decode(p, ord, g2, &x, &y, &z);
+    else { in2 = g2 < G; z = (int)(g2 % p.Z); y = (int)((g2 / p.Z) % p.Y); x = (int)(g2 / p.Z / p.Y); }
+    in_grid = in2;
+    lin = in2 ? ((int64_t)x * p.Y + y) * p.Z + z : -1;
+  }
   // means.  The count and the linear index of the voxel a lane accumulates for (group grp) live in lane group_src_lane(grp).
   if constexpr (EPI == 0 && LPV >= 4) {
     // z-run mapping: groups 4r .. 4r+3 of a lane are 4 consecutive lanes' voxels.  A run leaves as one 16-byte store per channel
@@ -291,11 +324,11 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
     // 16-byte aligned volume (then every plane's run is 16-byte aligned); otherwise (ragged bricks, Z % 4 != 0, odd grids,
     // offset output views) that run is stored element by element.  Decided per run; all shuffles are outside the branches.
     const bool vec_ok = (G & 3) == 0 && (reinterpret_cast<uintptr_t>(volume) & 15) == 0;
-    const int c = c0 + 4 * sub;
+    const int c = c0 + CPL * sub;
 #pragma unroll
     for (int r = 0; r < LPV / 4; ++r) {
       int64_t gv[4];
-      float m[4][4];
+      float m[4][CPL];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
         const int src = group_src_lane<LPV, EPI>(4 * r + k, vsel);
@@ -303,21 +336,25 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
         const int lo = __shfl((int)(lin & 0xffffffffLL), src, 64), hi = __shfl((int)(lin >> 32), src, 64);
         gv[k] = ((int64_t)hi << 32) | (uint32_t)lo;
         const float denom = (float)cv;
-        const float4 a = acc[4 * r + k];
-        m[k][0] = cv > 0 ? a.x / denom : 0.0f; m[k][1] = cv > 0 ? a.y / denom : 0.0f;
-        m[k][2] = cv > 0 ? a.z / denom : 0.0f; m[k][3] = cv > 0 ? a.w / denom : 0.0f;
+#pragma unroll
+        for (int h = 0; h < Q; ++h) {
+          const float4 a = acc[(4 * r + k) * Q + h];
+          m[k][4 * h + 0] = cv > 0 ? a.x / denom : 0.0f; m[k][4 * h + 1] = cv > 0 ? a.y / denom : 0.0f;
+          m[k][4 * h + 2] = cv > 0 ? a.z / denom : 0.0f; m[k][4 * h + 3] = cv > 0 ? a.w / denom : 0.0f;
+        }
       }
       const bool whole = vec_ok && gv[0] >= 0 && (gv[0] & 3) == 0 && gv[1] == gv[0] + 1 && gv[2] == gv[0] + 2 && gv[3] == gv[0] + 3;
       if (whole) {
         float* o = volume + (int64_t)c * G + gv[0];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) store_run(o + j * G, m[0][j], m[1][j], m[2][j], m[3][j], ord.nt);
+        for (int j = 0; j < CPL; ++j) store_run(o + j * G, m[0][j], m[1][j], m[2][j], m[3][j], ord.nt);
       } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
           if (gv[k] >= 0) {
             float* o = volume + (int64_t)c * G + gv[k];
-            o[0] = m[k][0]; o[G] = m[k][1]; o[2 * G] = m[k][2]; o[3 * G] = m[k][3];
+#pragma unroll
+            for (int j = 0; j < CPL; ++j) o[j * G] = m[k][j];
           }
       }
     }
@@ -330,15 +367,18 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const float* _
       const int64_t gv = ((int64_t)hi << 32) | (uint32_t)lo;
       if (gv >= 0) {
         const float denom = (float)cv;
-        const float4 a = acc[grp];
-        const int c = c0 + 4 * sub;
-        const float m0 = cv > 0 ? a.x / denom : 0.0f, m1 = cv > 0 ? a.y / denom : 0.0f, m2 = cv > 0 ? a.z / denom : 0.0f,
-                    m3 = cv > 0 ? a.w / denom : 0.0f;
-        float* o = volume + (int64_t)c * G + gv;
-        if (ord.nt == 1) {                      // streaming stores: the volume is written once and not read here
-          __builtin_nontemporal_store(m0, o); __builtin_nontemporal_store(m1, o + G);
-          __builtin_nontemporal_store(m2, o + 2 * G); __builtin_nontemporal_store(m3, o + 3 * G);
-        } else { o[0] = m0; o[G] = m1; o[2 * G] = m2; o[3 * G] = m3; }
+#pragma unroll
+        for (int h = 0; h < Q; ++h) {
+          const float4 a = acc[grp * Q + h];
+          const int c = c0 + CPL * sub + 4 * h;
+          const float m0 = cv > 0 ? a.x / denom : 0.0f, m1 = cv > 0 ? a.y / denom : 0.0f, m2 = cv > 0 ? a.z / denom : 0.0f,
+                      m3 = cv > 0 ? a.w / denom : 0.0f;
+          float* o = volume + (int64_t)c * G + gv;
+          if (ord.nt == 1) {                      // streaming stores: the volume is written once and not read here
+            __builtin_nontemporal_store(m0, o); __builtin_nontemporal_store(m1, o + G);
+            __builtin_nontemporal_store(m2, o + 2 * G); __builtin_nontemporal_store(m3, o + 3 * G);
+          } else { o[0] = m0; o[G] = m1; o[2 * G] = m2; o[3 * G] = m3; }
+        }
       }
     }
   } else {
@@ -424,6 +464,26 @@ __global__ __launch_bounds__(256, PIPE == 1 ? 4 : 3) void backproject_accum_pipe
     }
     accum_block<LPV, PIPE, EPI>(p, feat, proj, volume, count, lb, sweep * (4 * LPV), sweep == 0, ord, lds_wave, (int)threadIdx.x);
   }
+}
+
+// The product schedule of the kernel above (one view in flight, z-run stores, free-running brick order) on 16-bit maps: a lane
+// gathers 8 channels per 16-byte load, so LPV lanes cover 8 * LPV channels per sweep.  OCC = waves per SIMD the register
+// budget is cut for (3 only for the 8-lane form, whose 64 accumulators + 32 gather registers do not fit 128).
+template <int LPV, int ELEM, int OCC>
+__global__ __launch_bounds__(256, OCC) void backproject_accum_h16_kernel(DenseParams p, const uint16_t* feat,
+                                                                         const float* __restrict__ proj,
+                                                                         float* __restrict__ volume,
+                                                                         int32_t* __restrict__ count, int chunk_blocks,
+                                                                         SlabOrder ord,
+                                                                         const uint16_t* const* __restrict__ feat_ref) {
+  if (feat_ref != nullptr) feat = *feat_ref;               // by reference, as backproject_accum_pipe_kernel
+  int64_t lb = blockIdx.x;
+  if (chunk_blocks > 0) {
+    const int64_t grp = lb & 7, k = lb >> 3;
+    lb = (grp + 8 * (k / chunk_blocks)) * chunk_blocks + k % chunk_blocks;
+  }
+  const int sweep = blockIdx.y;
+  accum_block<LPV, 1, 0, ELEM>(p, feat, proj, volume, count, lb, sweep * (8 * LPV), sweep == 0, ord, nullptr, (int)threadIdx.x);
 }
 
 #ifdef CNRMA_EXPERIMENTS
@@ -607,6 +667,57 @@ extern "C" int cnrma_backproject_accum_ref_f32(const float* const* feat_nhwc_ref
   if (feat_nhwc_ref == nullptr || C % 4 != 0) return CNRMA_EINVAL;
   return backproject_accum_any(nullptr, feat_nhwc_ref, proj, V, C, H, W, X, Y, Z, voxel_size, ox, oy, oz, volume, count,
                                workspace, workspace_bytes, stream);
+}
+
+// 16-bit maps: always the shipped schedule (DenseTune's defaults: brick order, one brick per XCD chunk); the A/B switches of the
+// experiments library only choose between the two C % 64 == 0 forms (lpv = 4 | 8)
+// lanes per voxel of the shipped C % 64 == 0 form: 8 = a whole 128-byte line per pixel and sweep at 3 waves per SIMD (168 VGPRs),
+// 4 = a 64-byte half line at 4 waves per SIMD (100 VGPRs); both free of scratch.  Measured at the north-star shape (DESIGN.md,
+// "Dense unprojection on 16-bit maps"; profiles/r08_dense_half_ab_ns.log): 4 lanes 10.47 / 10.42 ms (fp16 / bf16), 8 lanes
+// 10.63 / 10.61 ms -- the 4-lane form ships
+#define CNRMA_H16_LANES_C64 4
+
+template <int LPV, int OCC>
+static int launch_accum_h16(const DenseParams& p, const uint16_t* feat, const uint16_t* const* feat_ref, int elem, const float* proj,
+                            float* volume, int32_t* count, hipStream_t st) {
+  constexpr DenseTune t{};
+  SlabOrder ord{1, (int)ceil_div(p.X, t.st), (int)ceil_div(p.Y, t.st), (int)ceil_div(p.Z, t.zt), t.zt, t.st, t.tt, t.zi, t.nt, 0, 0, 8};
+  const int64_t cb = (int64_t)t.st * t.st * t.zt / 256;                  // one brick per chunk
+  const int64_t nb = (int64_t)ord.nsx * ord.nsy * ord.nsz * cb;
+  const int64_t gx = ceil_div(ceil_div(nb, cb), 8) * 8 * cb;             // whole chunks for every XCD group
+  dim3 grid((unsigned)gx, (unsigned)ceil_div(p.C, 8 * LPV));
+  if (elem == CNRMA_ELEM_F16)
+    hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_F16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
+                       (int)cb, ord, feat_ref);
+  else
+    hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_BF16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
+                       (int)cb, ord, feat_ref);
+  CNRMA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cnrma_backproject_accum_h16(const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem, const float* proj,
+                                           int V, int C, int H, int W, int X, int Y, int Z, float voxel_size, float ox, float oy,
+                                           float oz, float* volume, int32_t* count, void* workspace, int64_t workspace_bytes,
+                                           void* stream) {
+  (void)workspace; (void)workspace_bytes;                  // the lockstep schedules that use it have no 16-bit form
+  if (!elem16_known(elem) || (feat_nhwc == nullptr) == (feat_nhwc_ref == nullptr) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) != 0)
+    return CNRMA_EINVAL;
+  if (V <= 0 || C <= 0 || C % 8 != 0 || H <= 0 || W <= 0 || X <= 0 || Y <= 0 || Z <= 0) return CNRMA_EINVAL;
+  DenseParams p{V, C, H, W, X, Y, Z, voxel_size, ox, oy, oz};
+  hipStream_t st = as_stream(stream);
+  const uint16_t* f = static_cast<const uint16_t*>(feat_nhwc);
+  const uint16_t* const* fr = reinterpret_cast<const uint16_t* const*>(feat_nhwc_ref);
+#if defined(CNRMA_EXPERIMENTS) || CNRMA_H16_LANES_C64 == 8
+  int lanes64 = CNRMA_H16_LANES_C64;
+#ifdef CNRMA_EXPERIMENTS                // either C % 64 == 0 form by hand, for A/B runs (scripts/dense_half_ab.py)
+  if (CNRMA_DENSE_TUNE.lpv == 8 || CNRMA_DENSE_TUNE.lpv == 4) lanes64 = CNRMA_DENSE_TUNE.lpv;
+#endif
+  if (C % 64 == 0 && lanes64 == 8) return launch_accum_h16<8, 3>(p, f, fr, elem, proj, volume, count, st);
+#endif
+  if (C % 32 == 0) return launch_accum_h16<4, 4>(p, f, fr, elem, proj, volume, count, st);
+  if (C % 16 == 0) return launch_accum_h16<2, 4>(p, f, fr, elem, proj, volume, count, st);
+  return launch_accum_h16<1, 4>(p, f, fr, elem, proj, volume, count, st);
 }
 
 // Backward of the accumulate + mean w.r.t. the feature maps (training): volume[c][g] = sum_v feat[v][pix_v(g)][c] / count[g],

@@ -466,9 +466,10 @@ __global__ __launch_bounds__(256) void neus_scatter_records_kernel(int64_t R, co
   }
 }
 
-template <int LPR>
+// ELEM: 0 = fp32 maps; CNRMA_ELEM_F16 / CNRMA_ELEM_BF16 = 16-bit maps, widened exactly (FT = uint16_t)
+template <int LPR, int ELEM = 0, typename FT = float>
 __global__ __launch_bounds__(256) void neus_emit_rows_kernel(MarchParams p, int C, const float* __restrict__ proj_inv,
-                                                            const float* feat, const float* const* __restrict__ feat_ref,
+                                                            const FT* feat, const FT* const* __restrict__ feat_ref,
                                                             int64_t n_rows, const int32_t* __restrict__ n_rows_dev,
                                                             const int4* __restrict__ rec, EmitDst dst) {
   if (feat_ref != nullptr) feat = *feat_ref;         // feature maps handed over by reference (see cnrma_backproject_accum_ref_f32)
@@ -496,19 +497,35 @@ __global__ __launch_bounds__(256) void neus_emit_rows_kernel(MarchParams p, int 
     if (dst.sample) { dst.sample[2 * j] = (int32_t)r; dst.sample[2 * j + 1] = n; }
   }
   if (dst.feat) {
-    const float* f = feat + ((int64_t)view * p.H * p.W + pix) * C;
+    const FT* f = feat + ((int64_t)view * p.H * p.W + pix) * C;
     float* q = dst.feat + j * dst.feat_stride;
     const bool scaled = dst.w_div != nullptr;
     const float scale = scaled ? w / dst.w_div[0] : 1.0f;
-    const bool vec = ((C | dst.feat_stride) & 3) == 0 && ((((uintptr_t)dst.feat) | ((uintptr_t)feat)) & 15) == 0;
-    if (vec) {
-      for (int c = 4 * sub; c < C; c += 4 * LPR) {
-        float4 x = *reinterpret_cast<const float4*>(f + c);
-        if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; }
-        *reinterpret_cast<float4*>(q + c) = x;
+    if constexpr (ELEM == 0) {
+      const bool vec = ((C | dst.feat_stride) & 3) == 0 && ((((uintptr_t)dst.feat) | ((uintptr_t)feat)) & 15) == 0;
+      if (vec) {
+        for (int c = 4 * sub; c < C; c += 4 * LPR) {
+          float4 x = *reinterpret_cast<const float4*>(f + c);
+          if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; }
+          *reinterpret_cast<float4*>(q + c) = x;
+        }
+      } else {
+        for (int c = sub; c < C; c += LPR) q[c] = scaled ? f[c] * scale : f[c];
       }
     } else {
-      for (int c = sub; c < C; c += LPR) q[c] = scaled ? f[c] * scale : f[c];
+      // 8 channels per 16-byte load, two 16-byte stores
+      const bool vec = (C & 7) == 0 && (dst.feat_stride & 3) == 0 && ((((uintptr_t)dst.feat) | ((uintptr_t)feat)) & 15) == 0;
+      if (vec) {
+        for (int c = 8 * sub; c < C; c += 8 * LPR) {
+          float4 x, y;
+          elem16_x8<ELEM>(*reinterpret_cast<const uint4*>(f + c), &x, &y);
+          if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; y.x *= scale; y.y *= scale; y.z *= scale; y.w *= scale; }
+          *reinterpret_cast<float4*>(q + c) = x;
+          *reinterpret_cast<float4*>(q + c + 4) = y;
+        }
+      } else {
+        for (int c = sub; c < C; c += LPR) q[c] = scaled ? elem16_to_f32<ELEM>(f[c]) * scale : elem16_to_f32<ELEM>(f[c]);
+      }
     }
   }
 }
@@ -806,7 +823,8 @@ extern "C" int cnrma_nchw_to_nhwc_march_f32(const float* feat_nchw, float* feat_
                       sig_table ? reinterpret_cast<const uint8_t*>(skip_table) : nullptr);
 }
 
-static int neus_emit_rows_any(const float* proj_inv, const float* feat_nhwc, const float* const* feat_ref, int V, int C, int H, int W,
+template <int ELEM = 0, typename FT = float>
+static int neus_emit_rows_any(const float* proj_inv, const FT* feat_nhwc, const FT* const* feat_ref, int V, int C, int H, int W,
                                             int n_steps, float t_one, const int32_t* row_offset, int64_t n_out,
                                             const int32_t* n_out_dev, const void* kept, int cap,
                                             const int32_t* sel_index, int64_t sel_cap, void* records,
@@ -826,13 +844,13 @@ static int neus_emit_rows_any(const float* proj_inv, const float* feat_nhwc, con
     hipLaunchKernelGGL(neus_scatter_records_kernel, dim3((unsigned)ceil_div(R, 256)), dim3(256), 0, st, R, row_offset,
                        reinterpret_cast<const int2*>(kept), cap, sel_index, sel_cap, n_out, rec);
   if (C % 256 == 0) {      // one wave copies a row's 1-KiB channel vector per instruction
-    hipLaunchKernelGGL((neus_emit_rows_kernel<64>), dim3((unsigned)ceil_div(n_out * 64, 256)), dim3(256), 0, st, p, C,
+    hipLaunchKernelGGL((neus_emit_rows_kernel<64, ELEM, FT>), dim3((unsigned)ceil_div(n_out * 64, 256)), dim3(256), 0, st, p, C,
                        proj_inv, feat_nhwc, feat_ref, n_out, n_out_dev, rec, d);
   } else if (C % 32 == 0) {
-    hipLaunchKernelGGL((neus_emit_rows_kernel<8>), dim3((unsigned)ceil_div(n_out * 8, 256)), dim3(256), 0, st, p, C,
+    hipLaunchKernelGGL((neus_emit_rows_kernel<8, ELEM, FT>), dim3((unsigned)ceil_div(n_out * 8, 256)), dim3(256), 0, st, p, C,
                        proj_inv, feat_nhwc, feat_ref, n_out, n_out_dev, rec, d);
   } else {
-    hipLaunchKernelGGL((neus_emit_rows_kernel<2>), dim3((unsigned)ceil_div(n_out * 2, 256)), dim3(256), 0, st, p, C,
+    hipLaunchKernelGGL((neus_emit_rows_kernel<2, ELEM, FT>), dim3((unsigned)ceil_div(n_out * 2, 256)), dim3(256), 0, st, p, C,
                        proj_inv, feat_nhwc, feat_ref, n_out, n_out_dev, rec, d);
   }
   CNRMA_LAUNCH_CHECK();
@@ -846,7 +864,7 @@ extern "C" int cnrma_rma_neus_emit_rows_f32(const float* proj_inv, const float* 
                                             const float* w_div, float addx, float addy, float addz, float* out_xyz,
                                             int xyz_stride, float* out_w, int w_stride, float* out_feat,
                                             int feat_stride, int32_t* out_sample, void* stream) {
-  return neus_emit_rows_any(proj_inv, feat_nhwc, nullptr, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept, cap,
+  return neus_emit_rows_any<0, float>(proj_inv, feat_nhwc, nullptr, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept, cap,
                             sel_index, sel_cap, records, w_div, addx, addy, addz, out_xyz, xyz_stride, out_w, w_stride, out_feat,
                             feat_stride, out_sample, stream);
 }
@@ -859,9 +877,29 @@ extern "C" int cnrma_rma_neus_emit_rows_ref_f32(const float* proj_inv, const flo
                                                 int xyz_stride, float* out_w, int w_stride, float* out_feat,
                                                 int feat_stride, int32_t* out_sample, void* stream) {
   if (feat_nhwc_ref == nullptr) return CNRMA_EINVAL;
-  return neus_emit_rows_any(proj_inv, nullptr, feat_nhwc_ref, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept, cap,
+  return neus_emit_rows_any<0, float>(proj_inv, nullptr, feat_nhwc_ref, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept, cap,
                             sel_index, sel_cap, records, w_div, addx, addy, addz, out_xyz, xyz_stride, out_w, w_stride, out_feat,
                             feat_stride, out_sample, stream);
+}
+
+extern "C" int cnrma_rma_neus_emit_rows_h16(const float* proj_inv, const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem,
+                                            int V, int C, int H, int W, int n_steps, float t_one, const int32_t* row_offset,
+                                            int64_t n_out, const int32_t* n_out_dev, const void* kept, int cap,
+                                            const int32_t* sel_index, int64_t sel_cap, void* records, const float* w_div,
+                                            float addx, float addy, float addz, float* out_xyz, int xyz_stride, float* out_w,
+                                            int w_stride, float* out_feat, int feat_stride, int32_t* out_sample, void* stream) {
+  if (!elem16_known(elem) || (feat_nhwc == nullptr) == (feat_nhwc_ref == nullptr) || C % 8 != 0 ||
+      (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) != 0)
+    return CNRMA_EINVAL;
+  const uint16_t* f = static_cast<const uint16_t*>(feat_nhwc);
+  const uint16_t* const* fr = reinterpret_cast<const uint16_t* const*>(feat_nhwc_ref);
+  if (elem == CNRMA_ELEM_F16)
+    return neus_emit_rows_any<CNRMA_ELEM_F16, uint16_t>(proj_inv, f, fr, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept,
+                                                        cap, sel_index, sel_cap, records, w_div, addx, addy, addz, out_xyz, xyz_stride,
+                                                        out_w, w_stride, out_feat, feat_stride, out_sample, stream);
+  return neus_emit_rows_any<CNRMA_ELEM_BF16, uint16_t>(proj_inv, f, fr, V, C, H, W, n_steps, t_one, row_offset, n_out, n_out_dev, kept,
+                                                       cap, sel_index, sel_cap, records, w_div, addx, addy, addz, out_xyz, xyz_stride,
+                                                       out_w, w_stride, out_feat, feat_stride, out_sample, stream);
 }
 
 // Backward of the emission w.r.t. the feature maps (the only differentiable input: the weights are computed under

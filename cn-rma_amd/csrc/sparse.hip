@@ -766,8 +766,9 @@ __global__ __launch_bounds__(256) void absmax_kernel(const float* __restrict__ i
 // over in VOXEL order (the voxeliser carried the 16-byte records through its representative selection and sort), so the
 // sparse tensor's feature rows are written once, in place, with their magnitude bound: no [M, C] intermediate, no row gather,
 // no absmax pass.  LPR lanes per row.
-template <int LPR>
-__global__ __launch_bounds__(256) void emit_features_kernel(const float* feat, const float* const* __restrict__ feat_ref, int C,
+// ELEM: 0 = fp32 maps; CNRMA_ELEM_F16 / CNRMA_ELEM_BF16 = 16-bit maps, widened exactly (FT = uint16_t; 8 channels per 16-byte load)
+template <int LPR, int ELEM = 0, typename FT = float>
+__global__ __launch_bounds__(256) void emit_features_kernel(const FT* feat, const FT* const* __restrict__ feat_ref, int C,
                                                             const int4* __restrict__ rec, int64_t n_cap,
                                                             const int32_t* __restrict__ n_dev, const float* __restrict__ w_div,
                                                             float* __restrict__ out, int out_stride, float* __restrict__ out_amax) {
@@ -779,23 +780,44 @@ __global__ __launch_bounds__(256) void emit_features_kernel(const float* feat, c
   if (j < live_rows(n_cap, n_dev)) {
     const int4 rc = rec[j];
     const float w = __int_as_float(rc.z);
-    const float* f = feat + (int64_t)rc.x * C;
+    const FT* f = feat + (int64_t)rc.x * C;
     float* q = out + j * out_stride;
     const bool scaled = w_div != nullptr;
     const float scale = scaled ? w / w_div[0] : 1.0f;
-    const bool vec = ((C | out_stride) & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)feat)) & 15) == 0;
-    if (vec) {
-      for (int c = 4 * sub; c < C; c += 4 * LPR) {
-        float4 x = *reinterpret_cast<const float4*>(f + c);
-        if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; }
-        *reinterpret_cast<float4*>(q + c) = x;
-        mx = fmaxf(fmaxf(mx, fabsf(x.x)), fmaxf(fmaxf(fabsf(x.y), fabsf(x.z)), fabsf(x.w)));
+    if constexpr (ELEM == 0) {
+      const bool vec = ((C | out_stride) & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)feat)) & 15) == 0;
+      if (vec) {
+        for (int c = 4 * sub; c < C; c += 4 * LPR) {
+          float4 x = *reinterpret_cast<const float4*>(f + c);
+          if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; }
+          *reinterpret_cast<float4*>(q + c) = x;
+          mx = fmaxf(fmaxf(mx, fabsf(x.x)), fmaxf(fmaxf(fabsf(x.y), fabsf(x.z)), fabsf(x.w)));
+        }
+      } else {
+        for (int c = sub; c < C; c += LPR) {
+          const float x = scaled ? f[c] * scale : f[c];
+          q[c] = x;
+          mx = fmaxf(mx, fabsf(x));
+        }
       }
     } else {
-      for (int c = sub; c < C; c += LPR) {
-        const float x = scaled ? f[c] * scale : f[c];
-        q[c] = x;
-        mx = fmaxf(mx, fabsf(x));
+      const bool vec = (C & 7) == 0 && (out_stride & 3) == 0 && ((((uintptr_t)out) | ((uintptr_t)feat)) & 15) == 0;
+      if (vec) {
+        for (int c = 8 * sub; c < C; c += 8 * LPR) {
+          float4 x, y;
+          elem16_x8<ELEM>(*reinterpret_cast<const uint4*>(f + c), &x, &y);
+          if (scaled) { x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale; y.x *= scale; y.y *= scale; y.z *= scale; y.w *= scale; }
+          *reinterpret_cast<float4*>(q + c) = x;
+          *reinterpret_cast<float4*>(q + c + 4) = y;
+          mx = fmaxf(fmaxf(mx, fabsf(x.x)), fmaxf(fmaxf(fabsf(x.y), fabsf(x.z)), fabsf(x.w)));
+          mx = fmaxf(fmaxf(mx, fabsf(y.x)), fmaxf(fmaxf(fabsf(y.y), fabsf(y.z)), fabsf(y.w)));
+        }
+      } else {
+        for (int c = sub; c < C; c += LPR) {
+          const float x = scaled ? elem16_to_f32<ELEM>(f[c]) * scale : elem16_to_f32<ELEM>(f[c]);
+          q[c] = x;
+          mx = fmaxf(mx, fabsf(x));
+        }
       }
     }
   }
@@ -3920,6 +3942,37 @@ extern "C" int cnrma_rma_emit_features_f32(const float* feat_nhwc, const float* 
                        feat_nhwc_ref, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax);
   CNRMA_LAUNCH_CHECK();
   return 0;
+}
+
+template <int ELEM>
+static int emit_features_h16(const uint16_t* feat, const uint16_t* const* feat_ref, int C, const int4* rec, int64_t n_cap,
+                             const int32_t* n_dev, const float* w_div, float* out_feat, int feat_stride, float* out_amax,
+                             hipStream_t st) {
+  if (C % 256 == 0)
+    hipLaunchKernelGGL((emit_features_kernel<64, ELEM, uint16_t>), dim3((unsigned)ceil_div(n_cap * 64, 256)), dim3(256), 0, st, feat,
+                       feat_ref, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax);
+  else if (C % 32 == 0)
+    hipLaunchKernelGGL((emit_features_kernel<8, ELEM, uint16_t>), dim3((unsigned)ceil_div(n_cap * 8, 256)), dim3(256), 0, st, feat,
+                       feat_ref, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax);
+  else
+    hipLaunchKernelGGL((emit_features_kernel<2, ELEM, uint16_t>), dim3((unsigned)ceil_div(n_cap * 2, 256)), dim3(256), 0, st, feat,
+                       feat_ref, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax);
+  CNRMA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cnrma_rma_emit_features_h16(const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem, int C,
+                                           const void* records, int64_t n_cap, const int32_t* n_dev, const float* w_div,
+                                           float* out_feat, int feat_stride, float* out_amax, void* stream) {
+  if (!elem16_known(elem) || (feat_nhwc == nullptr) == (feat_nhwc_ref == nullptr) || C <= 0 || C % 8 != 0 ||
+      (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) != 0 || records == nullptr || out_feat == nullptr || n_cap <= 0 || feat_stride < C)
+    return CNRMA_EINVAL;
+  const uint16_t* f = static_cast<const uint16_t*>(feat_nhwc);
+  const uint16_t* const* fr = reinterpret_cast<const uint16_t* const*>(feat_nhwc_ref);
+  const int4* rec = reinterpret_cast<const int4*>(records);
+  if (elem == CNRMA_ELEM_F16)
+    return emit_features_h16<CNRMA_ELEM_F16>(f, fr, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax, as_stream(stream));
+  return emit_features_h16<CNRMA_ELEM_BF16>(f, fr, C, rec, n_cap, n_dev, w_div, out_feat, feat_stride, out_amax, as_stream(stream));
 }
 
 extern "C" int cnrma_absmax_f32(const float* in, int64_t n_cap, const int32_t* n_dev, int C, float* out_amax,

@@ -248,6 +248,65 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_v4_kernel(const float* __res
   }
 }
 
+// The same transposes for 16-bit elements of either type (bits are moved, never interpreted).
+__global__ __launch_bounds__(256) void nchw_to_nhwc_b16_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int C,
+                                                               int64_t HW) {
+  __shared__ uint16_t tile[32][65];
+  const int64_t view = blockIdx.z;
+  const int64_t p0 = (int64_t)blockIdx.x * 64;
+  const int c0 = blockIdx.y * 32;
+  const uint16_t* s = src + view * C * HW;
+  uint16_t* d = dst + view * C * HW;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;  // 64 x 4
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    int c = c0 + ty + 4 * j;
+    int64_t p = p0 + tx;
+    tile[ty + 4 * j][tx] = (c < C && p < HW) ? s[(int64_t)c * HW + p] : (uint16_t)0;
+  }
+  __syncthreads();
+  const int cx = threadIdx.x & 31, py = threadIdx.x >> 5;  // 32 x 8
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    int c = c0 + cx;
+    int64_t p = p0 + py + 8 * j;
+    if (c < C && p < HW) d[p * C + c] = tile[cx][py + 8 * j];
+  }
+}
+
+// 64 channels x 64 pixels per block with 16-byte accesses on both sides: a lane reads 8 pixels of one channel row and writes
+// 8 channels of one pixel row.  Needs HW % 8 == 0 and C % 8 == 0.
+__global__ __launch_bounds__(256) void nchw_to_nhwc_b16_v8_kernel(const uint16_t* __restrict__ src, uint16_t* __restrict__ dst, int C,
+                                                                  int64_t HW) {
+  __shared__ uint16_t tile[64][66];          // 33-word rows: a column walk changes bank with every row
+  const int64_t view = blockIdx.z;
+  const int64_t p0 = (int64_t)blockIdx.x * 64;
+  const int c0 = blockIdx.y * 64;
+  const uint16_t* s = src + view * C * HW;
+  uint16_t* d = dst + view * C * HW;
+  const int q = threadIdx.x & 7, r = threadIdx.x >> 3;      // 8 octets x 32 rows
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int c = r + 32 * j;
+    uint4 v = make_uint4(0u, 0u, 0u, 0u);
+    if (c0 + c < C && p0 + 8 * q < HW) v = *reinterpret_cast<const uint4*>(s + (int64_t)(c0 + c) * HW + p0 + 8 * q);
+    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { tile[c][8 * q + 2 * i] = (uint16_t)(w[i] & 0xffffu); tile[c][8 * q + 2 * i + 1] = (uint16_t)(w[i] >> 16); }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < 2; ++j) {
+    const int p = r + 32 * j;
+    if (c0 + 8 * q < C && p0 + p < HW) {
+      uint32_t w[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w[i] = (uint32_t)tile[8 * q + 2 * i][p] | ((uint32_t)tile[8 * q + 2 * i + 1][p] << 16);
+      *reinterpret_cast<uint4*>(d + (p0 + p) * C + c0 + 8 * q) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+  }
+}
+
 // ---- exact-count uniform random subset (device replacement of np.random.choice(M, n_keep, replace=False)) ----------
 // every row gets a 32-bit hash key of (seed, index); the n_keep smallest keys are kept (radix select through two
 // 16-bit histograms); ties on the threshold key are broken by index, so the result is deterministic for a seed.
@@ -690,6 +749,23 @@ extern "C" int cnrma_nchw_to_nhwc_f32(const float* feat_nchw, float* feat_nhwc, 
   }
   dim3 grid((unsigned)ceil_div(HW, 64), (unsigned)ceil_div(C, 32), (unsigned)V);
   hipLaunchKernelGGL(nchw_to_nhwc_kernel, grid, dim3(256), 0, as_stream(stream), feat_nchw, feat_nhwc, C, HW);
+  CNRMA_LAUNCH_CHECK();
+  return 0;
+}
+
+extern "C" int cnrma_nchw_to_nhwc_b16(const void* feat_nchw, void* feat_nhwc, int V, int C, int H, int W, void* stream) {
+  if (V <= 0 || C <= 0 || H <= 0 || W <= 0 || feat_nchw == nullptr || feat_nhwc == nullptr) return CNRMA_EINVAL;
+  const int64_t HW = (int64_t)H * W;
+  const uint16_t* s = static_cast<const uint16_t*>(feat_nchw);
+  uint16_t* d = static_cast<uint16_t*>(feat_nhwc);
+  if (HW % 8 == 0 && C % 8 == 0 && ((((uintptr_t)feat_nchw) | ((uintptr_t)feat_nhwc)) & 15) == 0) {
+    dim3 grid8((unsigned)ceil_div(HW, 64), (unsigned)ceil_div(C, 64), (unsigned)V);
+    hipLaunchKernelGGL(nchw_to_nhwc_b16_v8_kernel, grid8, dim3(256), 0, as_stream(stream), s, d, C, HW);
+    CNRMA_LAUNCH_CHECK();
+    return 0;
+  }
+  dim3 grid((unsigned)ceil_div(HW, 64), (unsigned)ceil_div(C, 32), (unsigned)V);
+  hipLaunchKernelGGL(nchw_to_nhwc_b16_kernel, grid, dim3(256), 0, as_stream(stream), s, d, C, HW);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }

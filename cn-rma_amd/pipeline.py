@@ -138,13 +138,15 @@ def forward_scenes(cfg, backbone, head, scenes):
 
 @torch.no_grad()
 def forward_scene(cfg, backbone, head, features_nchw, projections, tsdf, offset=(0.0, 0.0, 0.0), dense=True,
-                  timing=False, mask=None, proj_inv=None):
+                  timing=False, mask=None, proj_inv=None, keep_half=False):
     """One scene forward.  features_nchw [V,C,H,W] device fp32 (the 2D backbone's layout), projections [V,3,4]
     (full-resolution pixel units; a host copy avoids a D2H), tsdf [X,Y,Z] device.  Returns a dict with the decoded
-    boxes/scores and the intermediate sizes needed to recompute the algorithmic bytes."""
+    boxes/scores and the intermediate sizes needed to recompute the algorithmic bytes.
+    keep_half: fp16 / bf16 maps stay 16-bit and the dense unprojection and the NeuS row emission read them in place (same
+    results, bit for bit, as on the maps widened to fp32 -- which is what happens by default); depth mode widens them."""
     tm = StageTimer(timing)
     tm.mark("start")
-    feats = rma.to_nhwc(features_nchw)
+    feats = rma.to_nhwc(features_nchw, keep_dtype=keep_half)
     tm.mark("nhwc")
     out = {}
     if dense:
@@ -296,8 +298,19 @@ class StaticScene:
     buffers, valid until the next run() of this object; `status` (device int32) counts violated capacity / branch
     assumptions -- non-zero means the scene outgrew the plan and must be re-run eagerly (forward_scene)."""
 
-    def __init__(self, cfg, backbone, head, device, margin=1.2, dense=True, stream=None, by_reference=True):
+    def __init__(self, cfg, backbone, head, device, margin=1.2, dense=True, stream=None, by_reference=True,
+                 feature_dtype=torch.float32):
+        """feature_dtype: the ONE element type of this slot's feature maps.  torch.float32 (default): maps of any dtype are
+        converted, as ever.  torch.float16 / torch.bfloat16 (NeuS mode, C % 8 == 0): the trace reads 16-bit maps -- in place when
+        they are channels-last in memory, through the 16-bit layout pass into a buffer of half the size otherwise -- and run()
+        with maps of another dtype raises ValueError (rounding fp32 maps to 16 bits silently is not a hand-off)."""
         self.cfg, self.backbone, self.head = cfg, backbone, head
+        self.feature_dtype = feature_dtype
+        if feature_dtype != torch.float32:
+            if feature_dtype not in rma.ELEM_CODES:
+                raise ValueError(f"feature_dtype must be torch.float32, torch.float16 or torch.bfloat16, got {feature_dtype}")
+            if cfg.ray_marching_type != "neus":
+                raise ValueError("16-bit feature maps are read by the NeuS path only: depth mode takes a float32 slot")
         self.device = torch.device(device)
         self.margin, self.dense = margin, dense
         # feature hand-off of channels-last maps (run()'s `by_reference` overrides it per scene): True = the trace reads the
@@ -316,6 +329,8 @@ class StaticScene:
     def _alloc_inputs(self, features_nchw, tsdf):
         V, C, H, W = features_nchw.shape
         dev = self.device
+        if self.feature_dtype != torch.float32 and C % 8 != 0:
+            raise ValueError(f"a {self.feature_dtype} slot needs C % 8 == 0 (one 16-byte load is 8 channels), got C = {C}")
         self.shape_nhwc = (V, H, W, C)
         # The kernels of the trace read the feature maps BY REFERENCE (feat_ref: a device word with their address, written per
         # scene): maps that are channels-last in memory -- what the 2D network hands over when it runs in
@@ -336,7 +351,8 @@ class StaticScene:
         self.march = self.march_out = None
         if cfg.ray_marching_type == "neus":
             self.march = rma._March(None, self.proj_inv, self.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps,
-                                    cfg.thr, "neus", 0, shape=self.shape_nhwc, device=dev, feat_ref=self.feat_ref)
+                                    cfg.thr, "neus", 0, shape=self.shape_nhwc, device=dev, feat_ref=self.feat_ref,
+                                    feat_dtype=self.feature_dtype)
             if self.march.kept_cap() <= 0:
                 raise _lib.CnrmaError("the static trace needs the single-march NeuS path (thr > 1/62)")
             self.march_out = self.march.march_buffers()
@@ -349,7 +365,7 @@ class StaticScene:
         """the slot's own channels-last feature buffer [V,H,W,C] (layout-pass target for NCHW inputs; producers may also write
         their output straight into it and call run(None, ...))"""
         if self.nhwc is None:
-            self.nhwc = torch.empty(self.shape_nhwc, dtype=torch.float32, device=self.device)
+            self.nhwc = torch.empty(self.shape_nhwc, dtype=self.feature_dtype, device=self.device)
             if self.march is not None:
                 self.march.feat = self.nhwc
         return self.nhwc
@@ -359,6 +375,9 @@ class StaticScene:
         run().  proj_inv: the
         [V,4,4] inverse of [P/stride; 0 0 0 1] when the caller pins it (parity tests: LAPACK's inverse is not bit-stable
         across host CPUs); computed here on the host like ray_marching.py:96-102 otherwise."""
+        if features_nchw is not None and self.feature_dtype != torch.float32 and features_nchw.dtype != self.feature_dtype:
+            raise ValueError(f"this slot reads {self.feature_dtype} feature maps, got {features_nchw.dtype}: convert them "
+                             "explicitly or use a slot of their dtype")
         if self._copied is not None:
             self._copied.synchronize()           # the previous scene's copies out of the pinned buffers have executed
         p = projections.detach().to("cpu", torch.float32)
@@ -379,13 +398,16 @@ class StaticScene:
         layout_from = None
         by_reference = self.by_reference if by_reference is None else bool(by_reference)
         self._held = None
+        in_place = rma.is_channels_last(features_nchw, (self.feature_dtype,))
+        if in_place and self.feature_dtype != torch.float32 and features_nchw.data_ptr() % 16 != 0:
+            by_reference = False                 # the 16-bit kernels load 16 bytes at a time: a misaligned view is copied
         if features_nchw is None:
             addr = self._nhwc_buffer().data_ptr()
-        elif rma.is_channels_last(features_nchw) and self.march is not None and by_reference:
+        elif in_place and self.march is not None and by_reference:
             assert tuple(features_nchw.shape) == (self.shape_nhwc[0], self.shape_nhwc[3], self.shape_nhwc[1], self.shape_nhwc[2])
             addr = features_nchw.data_ptr()
             self._held = features_nchw           # alive until this slot takes its next scene
-        elif rma.is_channels_last(features_nchw):
+        elif in_place:
             self._nhwc_buffer().copy_(features_nchw.permute(0, 2, 3, 1), non_blocking=True)
             addr = self.nhwc.data_ptr()
         else:
@@ -432,7 +454,8 @@ class StaticScene:
                 with torch.cuda.stream(side if side is not None else main):
                     out["volume"], out["count"] = rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin,
                                                                         cfg.stride, proj_scaled=self.proj_scaled,
-                                                                        feat_ref=self.feat_ref, shape=self.shape_nhwc)
+                                                                        feat_ref=self.feat_ref, shape=self.shape_nhwc,
+                                                                        feat_dtype=self.feature_dtype)
             fixed = cfg.sample_seed is not None          # a fixed seed: every replay draws the same subset (as forward_scene)
             coords, feats, n_sel, info = rma.aggregate_points_static(
                 self.nhwc, self.proj_inv, self.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
@@ -440,7 +463,7 @@ class StaticScene:
                 seed_dev=None if fixed else self.seed_dev,
                 marched=(self.march, self.march_out) if self.march is not None else None,
                 mode=cfg.ray_marching_type, select_grids=cfg.depth_points or 0, feat_ref=self.feat_ref, shape=self.shape_nhwc,
-                defer_feats=DEFER_POINT_FEATURES)
+                defer_feats=DEFER_POINT_FEATURES, feat_dtype=self.feature_dtype)
             moved = coords + self.offset_dev     # ray_marching.py:364 (one fp32 add per coordinate, as the reference)
             out.update(trace_net(plan, self.backbone, self.head, moved, feats, n_sel, cfg.voxel_size_fcaf3d, self.device,
                                  extra_counts=[info["M"], n_sel], late=info))
@@ -474,7 +497,8 @@ class StaticScene:
             plan = P.Plan(self.margin)
             with P.using(plan):
                 eager = forward_scene(self.cfg, self.backbone, self.head, features_nchw, projections, tsdf, dense=self.dense,
-                                      proj_inv=proj_inv, offset=_offset_list(offset))
+                                      proj_inv=proj_inv, offset=_offset_list(offset),
+                                      keep_half=self.feature_dtype != torch.float32)
         self.plan = plan if self.plan is None else self.plan.merge(plan)
         return eager
 
@@ -596,7 +620,7 @@ class StaticScene:
                 grown = P.Plan(self.margin)
                 with P.using(grown):
                     e = forward_scene(self.cfg, self.backbone, self.head, features_nchw, projections, tsdf, dense=self.dense,
-                                      offset=_offset_list(offset))
+                                      offset=_offset_list(offset), keep_half=self.feature_dtype != torch.float32)
             prev = getattr(self, "outgrown", None)
             same = prev is not None and len(prev.sizes) == len(grown.sizes) and len(prev.flags) == len(grown.flags)
             self.outgrown = prev.merge(grown) if same else grown

@@ -45,36 +45,55 @@ def scale_projection(projection, stride):
     return p
 
 
-def to_nhwc(features, out=None):
+# 16-bit feature maps (what a 2D stack run in half precision or under bf16 autocast hands over): dtype -> the C-ABI's element code.
+# The dense unprojection and the NeuS row emission read them where they lie: both widenings are exact and every sum stays fp32 in
+# view order, so the results are bit-identical to the fp32 kernels on `maps.float()`.  Everything else (depth mode, the legacy
+# cnrma_rma_neus_emit_f32 path, the autograd functions) widens them first, as before.
+ELEM_CODES = {torch.float16: 1, torch.bfloat16: 2}
+
+
+def _h16_readable(nhwc):
+    """can the 16-bit kernels read this [V,H,W,C] tensor in place?  (C % 8 == 0 and a 16-byte aligned base: one 16-byte load is 8
+    channels.)  Maps that cannot are widened and take the fp32 kernels -- same result."""
+    return nhwc.dtype in ELEM_CODES and nhwc.shape[-1] % 8 == 0 and nhwc.data_ptr() % 16 == 0 and nhwc.is_contiguous()
+
+
+def to_nhwc(features, out=None, keep_dtype=False):
     """features [V,C,H,W] (reference layout) -> channels-last [V,H,W,C] on the device (one HIP pass).
     A tensor whose MEMORY is already channels-last (torch.channels_last: what a 2D network run in that memory format
-    writes) is returned as a view -- no pass at all (25 GB of traffic at the north-star shape)."""
+    writes) is returned as a view -- no pass at all (25 GB of traffic at the north-star shape).
+    keep_dtype: fp16 / bf16 maps stay 16-bit (a view when channels-last in memory, cnrma_nchw_to_nhwc_b16 otherwise: half the
+    bytes, and the consumers read them in place); by default -- and for every other dtype -- the result is fp32."""
     _lib.require_gpu()
-    if (out is None and features.dim() == 4 and features.dtype == torch.float32 and features.is_cuda
-            and features.permute(0, 2, 3, 1).is_contiguous()):
+    dt = features.dtype if keep_dtype and features.dtype in ELEM_CODES else torch.float32
+    if out is None and is_channels_last(features, (dt,)):
         return features.permute(0, 2, 3, 1)
-    features = _f32(features)
+    features = features.contiguous() if dt != torch.float32 else _f32(features)
     V, C, H, W = features.shape
     if out is None:
-        out = torch.empty((V, H, W, C), dtype=torch.float32, device=features.device)
-    assert out.shape == (V, H, W, C) and out.is_contiguous() and out.dtype == torch.float32
-    call("cnrma_nchw_to_nhwc_f32", ptr(features), ptr(out), V, C, H, W, stream())
+        out = torch.empty((V, H, W, C), dtype=dt, device=features.device)
+    assert out.shape == (V, H, W, C) and out.is_contiguous() and out.dtype == dt
+    call("cnrma_nchw_to_nhwc_f32" if dt == torch.float32 else "cnrma_nchw_to_nhwc_b16", ptr(features), ptr(out), V, C, H, W, stream())
     return out
 
 
-def is_channels_last(features):
-    """[V,C,H,W] fp32 on the GPU whose MEMORY is channels-last (what a 2D network run in torch.channels_last writes): the
-    hot path reads such maps in place"""
-    return (torch.is_tensor(features) and features.dim() == 4 and features.dtype == torch.float32 and features.is_cuda
+def is_channels_last(features, dtypes=(torch.float32,)):
+    """[V,C,H,W] of one of `dtypes` (default: fp32) on the GPU whose MEMORY is channels-last (what a 2D network run in
+    torch.channels_last writes): the hot path reads such maps in place"""
+    return (torch.is_tensor(features) and features.dim() == 4 and features.dtype in dtypes and features.is_cuda
             and features.permute(0, 2, 3, 1).is_contiguous())
 
 
-def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stride, proj_scaled=None, feat_ref=None, shape=None):
+def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stride, proj_scaled=None, feat_ref=None, shape=None,
+                      feat_dtype=torch.float32):
     """Dense unprojection of all views + mean (ray_marching.py:21-69, :220-257) in one kernel.
 
-    features_nhwc [V,H,W,C] device fp32; projections [V,3,4] full-resolution (scaled here by `stride`), or
+    features_nhwc [V,H,W,C] device fp32, fp16 or bf16; projections [V,3,4] full-resolution (scaled here by `stride`), or
     proj_scaled [V,3,4] = scale_projection(projections, stride) already on the device (no host work at all).
-    Returns volume [C,X,Y,Z] (mean over the views that see the voxel, 0 elsewhere) and count [X,Y,Z] int32;
+    16-bit maps are read in place (cnrma_backproject_accum_h16; bit-identical to the fp32 kernel on `features_nhwc.float()`)
+    when C % 8 == 0 and their base is 16-byte aligned; otherwise they are widened first -- the result is the same.  By
+    reference (feat_ref), `feat_dtype` names the element type of the maps behind the address.
+    Returns volume [C,X,Y,Z] fp32 (mean over the views that see the voxel, 0 elsewhere) and count [X,Y,Z] int32;
     the reference's `valid` is `count > 0`.
     """
     _lib.require_gpu()
@@ -91,12 +110,19 @@ def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stri
     count = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
     st = stream()
     ws = _dense_workspace(dev, st)
+    tail = (ptr(proj), V, C, H, W, X, Y, Z, float(voxel_size), float(origin[0]), float(origin[1]), float(origin[2]), ptr(volume),
+            ptr(count), ptr(ws), ws.numel() * 4, st)
     if feat_ref is not None:
-        call("cnrma_backproject_accum_ref_f32", ptr(feat_ref), ptr(proj), V, C, H, W, X, Y, Z, float(voxel_size),
-             float(origin[0]), float(origin[1]), float(origin[2]), ptr(volume), ptr(count), ptr(ws), ws.numel() * 4, st)
+        if feat_dtype in ELEM_CODES:
+            call("cnrma_backproject_accum_h16", None, ptr(feat_ref), ELEM_CODES[feat_dtype], *tail)
+        else:
+            call("cnrma_backproject_accum_ref_f32", ptr(feat_ref), *tail)
+    elif _h16_readable(features_nhwc):
+        call("cnrma_backproject_accum_h16", ptr(features_nhwc), None, ELEM_CODES[features_nhwc.dtype], *tail)
     else:
-        call("cnrma_backproject_accum_f32", ptr(features_nhwc), ptr(proj), V, C, H, W, X, Y, Z, float(voxel_size),
-             float(origin[0]), float(origin[1]), float(origin[2]), ptr(volume), ptr(count), ptr(ws), ws.numel() * 4, st)
+        if features_nhwc.dtype in ELEM_CODES:            # odd channel count or base address: widen, same result
+            features_nhwc = _f32(features_nhwc)
+        call("cnrma_backproject_accum_f32", ptr(features_nhwc), *tail)
     return volume, count
 
 
@@ -205,9 +231,19 @@ class _March:
     """Argument pack shared by the count / emit calls of one scene."""
 
     def __init__(self, features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, mode, select_grids, shape=None,
-                 device=None, feat_ref=None):
+                 device=None, feat_ref=None, feat_dtype=None):
         """features_nhwc [V,H,W,C], or None with `shape` = (V,H,W,C) and `device`: the maps then come by reference
-        (feat_ref: device int64 [1] holding their address) or are bound later (bind_features)"""
+        (feat_ref: device int64 [1] holding their address) or are bound later (self.feat).
+        feat_dtype: element type of maps that come by reference or later (default fp32; given maps bring their own).  fp16 /
+        bf16 maps are read in place by the row emission of the single-march NeuS path; depth mode, the legacy emission
+        (thr <= 1/62) and maps the 16-bit kernels cannot read (C % 8 != 0, misaligned base) are widened to fp32 here."""
+        thr_ = float(thr) if thr is not None else 0.0
+        if features_nhwc is not None:
+            feat_dtype = features_nhwc.dtype
+            if feat_dtype in ELEM_CODES and not (mode == "neus" and thr_ > 1.0 / 62.0 and _h16_readable(features_nhwc)):
+                features_nhwc, feat_dtype = _f32(features_nhwc), torch.float32
+        self.feat_dtype = feat_dtype if feat_dtype is not None else torch.float32
+        self.elem = ELEM_CODES.get(self.feat_dtype, 0)        # 0: fp32 maps
         self.feat = features_nhwc
         self.feat_ref = feat_ref
         self.V, self.H, self.W, self.C = features_nhwc.shape if features_nhwc is not None else shape
@@ -220,7 +256,7 @@ class _March:
         self.org = [float(x) for x in origin]
         self.N = int(n_steps)
         self.t_one = float(step_length(dims, voxel_size, n_steps))
-        self.thr = float(thr) if thr is not None else 0.0
+        self.thr = thr_
         self.mode = mode
         self.k = int(select_grids or 0)
         self.R = self.V * self.H * self.W
@@ -267,7 +303,13 @@ class _March:
             call("cnrma_rma_march_tables_f32", ptr(self.tsdf), self.X, self.Y, self.Z, ptr(tab), ptr(skip), stream())
         tail = (ptr(self.pinv), ptr(self.tsdf), ptr(tab), self.V, self.H, self.W, self.X, self.Y, self.Z, self.vs, *self.org,
                 self.N, self.t_one, self.thr, ptr(cnt), ptr(wsum), ptr(kept), cap, ptr(overflow_all), ptr(skip), stream())
-        if layout_from is not None:
+        if layout_from is not None and self.elem:        # 16-bit maps: the layout pass of their width, then the march (two launches)
+            src = layout_from.contiguous()
+            assert (tuple(src.shape) == (self.V, self.C, self.H, self.W) and src.dtype == self.feat_dtype and self.feat is not None
+                    and self.feat.is_contiguous() and self.feat.dtype == self.feat_dtype)
+            call("cnrma_nchw_to_nhwc_b16", ptr(src), ptr(self.feat), self.V, self.C, self.H, self.W, stream())
+            call("cnrma_rma_neus_march_f32", *tail)
+        elif layout_from is not None:
             src = _f32(layout_from)
             assert tuple(src.shape) == (self.V, self.C, self.H, self.W) and self.feat is not None and self.feat.is_contiguous()
             call("cnrma_nchw_to_nhwc_march_f32", ptr(src), ptr(self.feat), self.C, *tail)
@@ -282,13 +324,20 @@ class _March:
                 torch.empty((self.R, cap, 2), dtype=torch.int32, device=self.dev),
                 torch.empty(4, dtype=torch.int32, device=self.dev), torch.empty_like(self.tsdf) if SIGMOID_TABLE else None)
 
+    def _emit_rows_head(self):
+        """entry point of the row emission for this scene's maps (fp32 / 16-bit, direct / by reference) + its leading arguments"""
+        by_ref = self.feat_ref is not None
+        if self.elem:
+            return ("cnrma_rma_neus_emit_rows_h16", ptr(self.pinv), None if by_ref else ptr(self.feat),
+                    ptr(self.feat_ref) if by_ref else None, self.elem)
+        return ("cnrma_rma_neus_emit_rows_ref_f32" if by_ref else "cnrma_rma_neus_emit_rows_f32", ptr(self.pinv),
+                ptr(self.feat_ref) if by_ref else ptr(self.feat))
+
     def emit_rows(self, row_offset, n_out, kept, sel_index, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat,
                   feat_stride, out_sample=None, n_out_dev=None):
         """n_out = rows of the output buffers; n_out_dev = device word with the live row count (None: all n_out)"""
         rec = torch.empty((int(n_out), 4), dtype=torch.int32, device=self.dev)
-        by_ref = self.feat_ref is not None
-        call("cnrma_rma_neus_emit_rows_ref_f32" if by_ref else "cnrma_rma_neus_emit_rows_f32", ptr(self.pinv),
-             ptr(self.feat_ref) if by_ref else ptr(self.feat), self.V, self.C, self.H, self.W, self.N,
+        call(*self._emit_rows_head(), self.V, self.C, self.H, self.W, self.N,
              self.t_one, ptr(row_offset), int(n_out), ptr(n_out_dev), ptr(kept), kept.shape[1], ptr(sel_index),
              sel_index.numel() if sel_index is not None else 0, ptr(rec), ptr(w_div), float(add[0]),
              float(add[1]), float(add[2]), out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride, ptr(out_sample),
@@ -297,16 +346,15 @@ class _March:
     def emit_records(self, rec, n_out, n_out_dev, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride,
                      out_sample=None):
         """emit_rows for records that are already selected and placed (select_records)"""
-        by_ref = self.feat_ref is not None
-        call("cnrma_rma_neus_emit_rows_ref_f32" if by_ref else "cnrma_rma_neus_emit_rows_f32", ptr(self.pinv),
-             ptr(self.feat_ref) if by_ref else ptr(self.feat), self.V, self.C, self.H, self.W, self.N,
+        call(*self._emit_rows_head(), self.V, self.C, self.H, self.W, self.N,
              self.t_one, None, int(n_out), ptr(n_out_dev), None, 0, None, 0, ptr(rec), ptr(w_div), float(add[0]),
              float(add[1]), float(add[2]), out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride, ptr(out_sample),
              stream())
 
     def emit(self, row_offset, sel_index, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride,
              out_sample=None, sel_cap=0, out_cap=0):
-        head = (ptr(self.pinv), ptr(self.tsdf), ptr(self.feat), self.V, self.C, self.H, self.W, self.X, self.Y, self.Z,
+        feat = _f32(self.feat) if self.elem else self.feat          # the legacy / depth emission reads fp32 maps only
+        head = (ptr(self.pinv), ptr(self.tsdf), ptr(feat), self.V, self.C, self.H, self.W, self.X, self.Y, self.Z,
                 self.vs, *self.org, self.N, self.t_one)
         tail = (ptr(row_offset), ptr(sel_index), ptr(w_div), float(add[0]), float(add[1]), float(add[2]),
                 out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride)
@@ -499,7 +547,8 @@ def aggregate_finish(st, readback, offset=(0.0, 0.0, 0.0), max_points=None, samp
 
 def aggregate_points_static(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps=300, thr=0.05,
                             offset=(0.0, 0.0, 0.0), max_points=None, seed=0, seed_dev=None, reference_quirks=True,
-                            marched=None, mode="neus", select_grids=0, feat_ref=None, shape=None, defer_feats=False):
+                            marched=None, mode="neus", select_grids=0, feat_ref=None, shape=None, defer_feats=False,
+                            feat_dtype=None):
     """aggregate_points() without a device->host read (the static trace of plan.Plan; NeuS single-march only): the row
     count M stays on the device, the selection always goes through the device sampler (it keeps every row when
     M <= max_points) and the outputs are capacity-sized.  Returns (coords [cap,3], feats [cap,C], n_dev int32 [1], info);
@@ -517,7 +566,7 @@ def aggregate_points_static(features_nhwc, proj_inv, tsdf, dims, voxel_size, ori
         cnt, wsum = m.count()
     else:
         m = _March(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, "neus", 0, shape=shape,
-                   device=proj_inv.device, feat_ref=feat_ref)
+                   device=proj_inv.device, feat_ref=feat_ref, feat_dtype=feat_dtype)
         if m.kept_cap() <= 0:
             raise _lib.CnrmaError("the static trace needs the single-march NeuS path (thr > 1/62)")
         cnt, wsum, kept, overflow = m.march()
@@ -560,8 +609,12 @@ def emit_point_features(info, rec, n_rows, n_dev, out=None, amax=None):
     if out is None:
         out = torch.empty((int(n_rows), m.C), dtype=torch.float32, device=m.dev)
     by_ref = m.feat_ref is not None
-    call("cnrma_rma_emit_features_f32", None if by_ref else ptr(m.feat), ptr(m.feat_ref) if by_ref else None, m.C, ptr(rec),
-         int(n_rows), ptr(n_dev), ptr(info["mean_w"]), ptr(out), out.shape[1], ptr(amax), stream())
+    head = (None if by_ref else ptr(m.feat), ptr(m.feat_ref) if by_ref else None)
+    tail = (m.C, ptr(rec), int(n_rows), ptr(n_dev), ptr(info["mean_w"]), ptr(out), out.shape[1], ptr(amax), stream())
+    if m.elem:
+        call("cnrma_rma_emit_features_h16", *head, m.elem, *tail)
+    else:
+        call("cnrma_rma_emit_features_f32", *head, *tail)
     return out
 
 

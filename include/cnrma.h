@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define CNRMA_EINVAL (-22)
-#define CNRMA_ABI_VERSION 6   /* 6: the cnrma_debug_* entry points (and the experimental kernels behind them) left the product library: they exist in libcnrma_hip_exp.so (-DCNRMA_EXPERIMENTS) only; no signature changed; 5: + cnrma_sparse_conv_prepare_weights_bf16_t, cnrma_sparse_conv_wgrad_go_bf16, cnrma_sparse_conv_go_bf16 (+ its weight images), cnrma_bn_train_forward_f32 / _backward_f32; 4: gather-once convolution family, records-based point selection (SampleWs layout), *_ref_f32 hand-off */
+#define CNRMA_ABI_VERSION 7   /* 7: + the 16-bit feature-map entry points cnrma_backproject_accum_h16, cnrma_rma_neus_emit_rows_h16, cnrma_rma_emit_features_h16, cnrma_nchw_to_nhwc_b16; no signature changed; 6: the cnrma_debug_* entry points (and the experimental kernels behind them) left the product library: they exist in libcnrma_hip_exp.so (-DCNRMA_EXPERIMENTS) only; no signature changed; 5: + cnrma_sparse_conv_prepare_weights_bf16_t, cnrma_sparse_conv_wgrad_go_bf16, cnrma_sparse_conv_go_bf16 (+ its weight images), cnrma_bn_train_forward_f32 / _backward_f32; 4: gather-once convolution family, records-based point selection (SampleWs layout), *_ref_f32 hand-off */
 
 int cnrma_abi_version(void);
 
@@ -74,6 +74,24 @@ int cnrma_backproject_accum_f32(const float* feat_nhwc, const float* proj, int V
 int cnrma_backproject_accum_ref_f32(const float* const* feat_nhwc_ref, const float* proj, int V, int C, int H, int W,
                                     int X, int Y, int Z, float voxel_size, float ox, float oy, float oz,
                                     float* volume, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* 16-bit feature maps, read where they lie (the reference runs its 2D stack in half precision under auto_fp16:
+ * backbone2d.py:61, fpn.py:150, resnet.py:374; test.py:186-188 wraps the model when a config sets fp16).
+ * elem: element type of the maps -- CNRMA_ELEM_F16 (IEEE half) or CNRMA_ELEM_BF16 (bfloat16). */
+#define CNRMA_ELEM_F16 1
+#define CNRMA_ELEM_BF16 2
+/* cnrma_backproject_accum_f32 / _ref_f32 (backproject() ray_marching.py:21-69, aggregate_2d_features() / clear_3d_features()
+ * :220-257) on 16-bit channels-last maps: exactly one of feat_nhwc (direct, 16-byte aligned) and feat_nhwc_ref (device word
+ * with the maps' address, which must be 16-byte aligned as well) is non-NULL.  C % 8 == 0: a lane gathers 8 channels per
+ * 16-byte load.  Both conversions to fp32 are exact and the sum stays fp32 in view order, so volume and count are bit-identical
+ * to cnrma_backproject_accum_f32 on the same maps widened to fp32.  CNRMA_EINVAL (nothing is launched) for an unknown elem,
+ * both or neither pointer, C % 8 != 0, a misaligned direct pointer, a bad dimension. */
+int cnrma_backproject_accum_h16(const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem, const float* proj, int V,
+                                int C, int H, int W, int X, int Y, int Z, float voxel_size, float ox, float oy, float oz,
+                                float* volume, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream);
+/* layout pass for 16-bit elements of either type (bits are moved, never interpreted): feat_nchw[V][C][H][W] -> feat_nhwc[V][H][W][C]
+ * (the 2D network's NCHW output, ray_marching.py:211-244, gathered as [b,:,py,px] at :64 and :799) */
+int cnrma_nchw_to_nhwc_b16(const void* feat_nchw, void* feat_nhwc, int V, int C, int H, int W, void* stream);
 
 #ifdef CNRMA_EXPERIMENTS
 /* libcnrma_hip_exp.so ONLY (built with -DCNRMA_EXPERIMENTS; the product library libcnrma_hip.so exports no cnrma_debug_* symbol
@@ -191,6 +209,19 @@ int cnrma_rma_neus_emit_rows_f32(const float* proj_inv, const float* feat_nhwc, 
                                  int feat_stride, int32_t* out_sample, void* stream);
 /* ... with the feature maps by reference (see cnrma_backproject_accum_ref_f32) */
 int cnrma_rma_neus_emit_rows_ref_f32(const float* proj_inv, const float* const* feat_nhwc_ref, int V, int C, int H, int W,
+                                 int n_steps, float t_one, const int32_t* row_offset, int64_t n_out,
+                                 const int32_t* n_out_dev, const void* kept, int cap, const int32_t* sel_index,
+                                 int64_t sel_cap, void* records, const float* w_div, float addx, float addy, float addz,
+                                 float* out_xyz, int xyz_stride, float* out_w, int w_stride, float* out_feat,
+                                 int feat_stride, int32_t* out_sample, void* stream);
+/* ... with 16-bit feature maps (elem: CNRMA_ELEM_F16 / CNRMA_ELEM_BF16), direct or by reference -- exactly one of the two
+ * pointers is non-NULL.  Replaces the gather features[b, :, v, u] * weights of ray_marching.py:289-307, :793-797 for maps the
+ * 2D stack wrote in half precision: out_feat = (float)h * (w / w_div[0]), the fp32 expression on the exactly widened element,
+ * so every output is bit-identical to cnrma_rma_neus_emit_rows_f32 on the widened maps; outputs stay fp32.  8 channels per
+ * 16-byte load where feat_stride % 4 == 0 and out_feat is 16-byte aligned, element by element otherwise.  CNRMA_EINVAL for an
+ * unknown elem, both or neither pointer, C % 8 != 0, a direct pointer that is not 16-byte aligned, a bad dimension. */
+int cnrma_rma_neus_emit_rows_h16(const float* proj_inv, const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem,
+                                 int V, int C, int H, int W,
                                  int n_steps, float t_one, const int32_t* row_offset, int64_t n_out,
                                  const int32_t* n_out_dev, const void* kept, int cap, const int32_t* sel_index,
                                  int64_t sel_cap, void* records, const float* w_div, float addx, float addy, float addz,
@@ -452,6 +483,12 @@ int cnrma_absmax_f32(const float* in, int64_t n_cap, const int32_t* n_dev, int C
  * cnrma_amax_bytes() ZEROED bytes, or NULL): no [M, C] intermediate, no row gather, no absmax pass.  Exactly one of feat_nhwc /
  * feat_nhwc_ref (see cnrma_backproject_accum_ref_f32) is given. */
 int cnrma_rma_emit_features_f32(const float* feat_nhwc, const float* const* feat_nhwc_ref, int C, const void* records,
+                                int64_t n_cap, const int32_t* n_dev, const float* w_div, float* out_feat, int feat_stride,
+                                float* out_amax, void* stream);
+/* ... with 16-bit feature maps (elem: CNRMA_ELEM_F16 / CNRMA_ELEM_BF16; ray_marching.py:298-307 on maps the 2D stack wrote in half
+ * precision): out_feat[j][:] = (float)h * (w_j / w_div[0]), bit-identical to cnrma_rma_emit_features_f32 on the widened maps.  The
+ * static trace of a 16-bit slot emits its point features through this one.  C % 8 == 0; a direct pointer is 16-byte aligned. */
+int cnrma_rma_emit_features_h16(const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem, int C, const void* records,
                                 int64_t n_cap, const int32_t* n_dev, const float* w_div, float* out_feat, int feat_stride,
                                 float* out_amax, void* stream);
 size_t cnrma_sparse_conv_f16_weight_bytes(int K, int Cin, int Cout);

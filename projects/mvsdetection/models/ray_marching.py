@@ -60,7 +60,7 @@ class RayMarching(MultiViewBase):
                  train_cfg=None, test_cfg=None, pretrained=None, use_feature_transform=True,
                  ray_marching_type="neus", depth_points=None, neus_threshold=None, middle_save_path=None,
                  middle_visualize_path=None, point_sampler="device", static_test=True, static_slots=3, static_calibration=2,
-                 static_feature_handoff="reference"):
+                 static_feature_handoff="reference", static_feature_dtype="float32"):
         super().__init__(pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin, backbone2d_stride,
                          backbone2d, feature_2d, backbone_3d, tsdf_head, save_path)
         self.detection_backbone = build_backbone(detection_backbone)
@@ -102,6 +102,12 @@ class RayMarching(MultiViewBase):
         if static_feature_handoff not in ("reference", "copy"):
             raise ValueError(f"static_feature_handoff must be 'reference' or 'copy', got {static_feature_handoff!r}")
         self.static_feature_handoff = static_feature_handoff
+        # element type of the graph path's feature maps: "float32" = everything is converted to fp32; "keep" = fp16 / bf16 maps
+        # (a 2D stack run in half precision or under bf16 autocast; NeuS marching, C % 8 == 0) are handed over unconverted and
+        # read in place -- same results bit for bit, no cast pass, half the slot buffer; slots are keyed by the maps' dtype
+        if static_feature_dtype not in ("float32", "keep"):
+            raise ValueError(f"static_feature_dtype must be 'float32' or 'keep', got {static_feature_dtype!r}")
+        self.static_feature_dtype = static_feature_dtype
         self._static = {}
         self._writer = None
         import atexit
@@ -366,7 +372,11 @@ class RayMarching(MultiViewBase):
         scene = inputs["scene"][0] if inputs.get("scene") is not None else None
         org = self.origin.view(-1).tolist()
         dense_in_graph = self.backbone3d is None
-        key = (tuple(feats.shape), tuple(self.voxel_dim), dense_in_graph, str(feats.device))
+        fdt = torch.float32
+        if (self.static_feature_dtype == "keep" and feats.dtype in rma.ELEM_CODES and feats.shape[1] % 8 == 0
+                and self.ray_marching_type == "neus"):
+            fdt = feats.dtype
+        key = (tuple(feats.shape), tuple(self.voxel_dim), dense_in_graph, str(feats.device), str(fdt))
         ctx = self._static.get(key)
         if ctx is not None and ctx["built"] and ctx["tag"] != pipeline.weights_tag(ctx["weights"]):
             # an optimiser step / in-place weight update since the capture: the graphs would replay stale weight images
@@ -378,7 +388,8 @@ class RayMarching(MultiViewBase):
                                        self.neus_threshold if self.ray_marching_type == "neus" else 0.05,
                                        self.max_points, self.voxel_size_fcaf3d, self.ray_marching_type, self.depth_points, "device")
             first = pipeline.StaticScene(cfg, self.detection_backbone, self.detection_head, feats.device, margin=self.static_margin,
-                                         dense=dense_in_graph, by_reference=self.static_feature_handoff == "reference")
+                                         dense=dense_in_graph, by_reference=self.static_feature_handoff == "reference",
+                                         feature_dtype=fdt)
             ctx = dict(cfg=cfg, slots=[first], pending=[None] * max(1, self.static_slots), seen=0, k=0, built=False,
                        weights=pipeline.weight_tensors(self.detection_backbone, self.detection_head), tag=None, grown=0)
             self._static[key] = ctx
@@ -401,10 +412,11 @@ class RayMarching(MultiViewBase):
         if not dense_in_graph:
             # the Atlas 3D network sits between the two halves (:313-318): dense volume (one kernel) -> torch modules -> TSDF.
             # The layout pass writes straight into the static buffer of the slot this scene runs on.
-            if rma.is_channels_last(feats):                  # the 2D network's own layout: read in place, nothing to convert
-                nhwc = rma.to_nhwc(feats)
+            keep = st.feature_dtype != torch.float32         # 16-bit slot: the maps stay 16-bit here as well
+            if rma.is_channels_last(feats, (st.feature_dtype,)):     # the 2D network's own layout: read in place, nothing to convert
+                nhwc = rma.to_nhwc(feats, keep_dtype=keep)
             else:
-                nhwc = rma.to_nhwc(feats, out=st._nhwc_buffer())
+                nhwc = rma.to_nhwc(feats, out=st._nhwc_buffer(), keep_dtype=keep)
                 loaded = True
             vol, cnt = rma.backproject_accum(nhwc, proj, self.voxel_dim, self.voxel_size, org, self.backbone2d_stride)
             self.volume, self.valid = vol.unsqueeze(0), (cnt > 0).view(1, 1, *cnt.shape)
@@ -438,7 +450,7 @@ class RayMarching(MultiViewBase):
         ctx["slots"] = [first]
         for _ in range(1, max(1, self.static_slots)):
             st = pipeline.StaticScene(ctx["cfg"], self.detection_backbone, self.detection_head, feats.device, margin=first.margin,
-                                      dense=dense_in_graph, by_reference=first.by_reference)
+                                      dense=dense_in_graph, by_reference=first.by_reference, feature_dtype=first.feature_dtype)
             st.build(feats, proj, tsdf, plan=first.plan)
             ctx["slots"].append(st)
         ctx["built"], ctx["grown"] = True, 0
@@ -519,7 +531,8 @@ class RayMarching(MultiViewBase):
         grown = P.Plan(st.margin)
         with P.using(grown):                                    # the eager pass reads the true sizes back and records them
             e = pipeline.forward_scene(ctx["cfg"], self.detection_backbone, self.detection_head, feats, proj, tsdf,
-                                       offset=pipeline._offset_list(offset), dense=st.dense)
+                                       offset=pipeline._offset_list(offset), dense=st.dense,
+                                       keep_half=st.feature_dtype != torch.float32)
         self._save_raw(e["bboxes"], e["scores"], item["scene"])
         prev = ctx.get("outgrown")
         same = prev is not None and len(prev.sizes) == len(grown.sizes) and len(prev.flags) == len(grown.flags)
