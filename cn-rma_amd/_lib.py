@@ -128,6 +128,8 @@ SIGNATURES = {
     "cnrma_nms_mask_f32": (c_int, [P, I, F, I, P, P]),
     "cnrma_box_iou_f32": (c_int, [P, I, P, I, I, I, P, P]),
     "cnrma_fcaf3d_scores_f32": (c_int, [P, P, L, I, P, P, P]),
+    "cnrma_nms_classes_workspace_bytes": (c_size_t, [I, I]),
+    "cnrma_nms_classes_f32": (c_int, [P, I, P, I, I, P, I, P, F, F, P, c_size_t, P, P, P, I, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -176,10 +176,61 @@ def forward_scene(cfg, backbone, head, features_nchw, projections, tsdf, offset=
     return out
 
 
-def trace_net(plan, backbone, head, coords, feats, n_dev, voxel_size, device, extra_counts=(), late=None):
+def trace_nms(plan, out, nms, state, nms_pre=0):
+    """the opt-in last stage of a static trace: per-class NMS of the padded detections on the device (postprocess.nms_device,
+    four launches on the same stream: the captured sequence stays a linear chain).  nms = dict(score_thr=..., iou_thr=...);
+    `state` belongs to the traced object and holds the workspace and the outputs, allocated by its first static run and pinned
+    for the life of the plan.  Adds nms_boxes / nms_scores / nms_labels (capacity-sized) and nms_n (device int32 [1]).
+    A level that keeps all its rows owns its whole capacity in the block, but the plan holds it to nms_pre live rows (more
+    is a violation: status != 0): such segments are cut to nms_pre rows first (two copies more), so that four levels of
+    nms_pre <= 1024 always fit the kernel's 4096 rows."""
+    from . import postprocess
+    b, sc, sizes = out["bboxes"], out["scores"], list(out["sizes"])
+    if nms_pre > 0 and any(k > nms_pre for k in sizes):
+        starts = [sum(sizes[:l]) for l in range(len(sizes))]
+        sizes = [min(k, nms_pre) for k in sizes]
+        b = torch.cat([b[r0:r0 + k] for r0, k in zip(starts, sizes)])
+        sc = torch.cat([sc[r0:r0 + k] for r0, k in zip(starts, sizes)])
+    if b.shape[0] > postprocess.NMS_DEVICE_MAX_ROWS:
+        raise _lib.CnrmaError(f"nms= needs a detection block of at most {postprocess.NMS_DEVICE_MAX_ROWS} rows, the plan's "
+                              f"levels {sizes} add up to {b.shape[0]}")
+    key = (b.shape[0], sc.shape[1], b.shape[1], b.device)
+    if state.get("key") != key:
+        state.clear()
+        state.update(key=key, bufs=postprocess.nms_device_buffers(b.shape[0], sc.shape[1], b.shape[1], b.device))
+    bufs = state["bufs"]
+    plan.keep(*bufs.values())
+    boxes, scores, labels, n = postprocess.nms_device(b, sc, valid=out["valid"], sizes=sizes, padded=True, out=bufs, **nms)
+    out.update(nms_boxes=boxes, nms_scores=scores, nms_labels=labels, nms_n=n)
+
+
+def check_nms_setting(nms):
+    if nms is not None and not (isinstance(nms, dict) and set(nms) <= {"score_thr", "iou_thr"}):
+        raise ValueError(f"nms must be None or dict(score_thr=..., iou_thr=...), got {nms!r}")
+    return None if nms is None else dict(nms)
+
+
+def final_detections(out):
+    """(boxes [K, 6|7], scores [K], labels [K]) of a static output traced with nms=...: what postprocess.nms makes of
+    detections(out), after ONE device->host read (status, valid, counts and the detection count together)"""
+    if "nms_n" not in out:
+        raise _lib.CnrmaError("this static trace was built without nms=...: it ends at the raw detections")
+    if out.get("done") is not None:
+        torch.cuda.current_stream(out["bboxes"].device).wait_event(out["done"])
+    host = _lib.read_ints(torch.cat((out["status"].view(-1), out["valid"].view(-1), out["counts"].view(-1),
+                                     out["nms_n"].view(-1))))
+    if host[0] != 0:
+        raise _lib.CnrmaError(f"{host[0]} capacity / branch assumption(s) of the static plan violated: re-run eagerly")
+    k = min(host[-1], out["nms_boxes"].shape[0])
+    return out["nms_boxes"][:k], out["nms_scores"][:k], out["nms_labels"][:k]
+
+
+def trace_net(plan, backbone, head, coords, feats, n_dev, voxel_size, device, extra_counts=(), late=None, nms=None,
+              nms_state=None):
     """the sparse half inside a static trace (plan.static): voxelise -> MinkResNet34 -> neck / head -> decode of the point
     rows [0, n_dev) of the capacity-sized (coords, feats).  Returns the padded detections, the per-level head outputs and
     one small tensor of live counts -- no device->host read.
+    nms (dict(score_thr, iou_thr), with the caller's nms_state): the per-class NMS is appended, see trace_nms.
     late (feats is None): the aggregation's info with the point RECORDS instead of features -- the voxeliser carries the
     16-byte records (as 4-float rows) through its representative selection and sort, and the features of the surviving rows
     are emitted straight into the sparse tensor, with their magnitude bound: no [M, C] intermediate, no row gather, no
@@ -199,10 +250,13 @@ def trace_net(plan, backbone, head, coords, feats, n_dev, voxel_size, device, ex
     # every live count of the pass in ONE small tensor (read together with the detections, if at all)
     counts = torch.cat([c.view(1) for c in extra_counts] + [x.cs.n_dev.view(1)] + [l.cs.n_dev.view(1) for l in levels] +
                        [c[0].n_dev.view(1) for c in css]).to(torch.int32)
-    return dict(bboxes=bboxes, scores=scores, valid=valid, sizes=sizes, status=status, counts=counts, n_levels=len(levels),
-                n_extra=len(extra_counts), levels=levels,
-                head=dict(centerness=[c[0] for c in cen], bbox_pred=[b[0] for b in box], cls_score=[c[0] for c in cls],
-                          points=[p[0] for p in pts], n_dev=[c[0].n_dev for c in css]))
+    out = dict(bboxes=bboxes, scores=scores, valid=valid, sizes=sizes, status=status, counts=counts, n_levels=len(levels),
+               n_extra=len(extra_counts), levels=levels,
+               head=dict(centerness=[c[0] for c in cen], bbox_pred=[b[0] for b in box], cls_score=[c[0] for c in cls],
+                         points=[p[0] for p in pts], n_dev=[c[0].n_dev for c in css]))
+    if nms is not None:
+        trace_nms(plan, out, nms, nms_state, (head.test_cfg.nms_pre or 0) if head.test_cfg is not None else 0)
+    return out
 
 
 class StaticNet:
@@ -210,8 +264,11 @@ class StaticNet:
     aggregation, without the geometric half in front.  Used to pin the graph path of the network to the oracle on
     arbitrary point sets (tests) and by callers that bring their own points."""
 
-    def __init__(self, backbone, head, voxel_size, device, margin=1.2, stream=None):
+    def __init__(self, backbone, head, voxel_size, device, margin=1.2, stream=None, nms=None):
+        """nms: None (the trace ends at the raw detections) or dict(score_thr=..., iou_thr=...): the per-class NMS runs on the
+        device at the end of the trace (out["nms_boxes" / "nms_scores" / "nms_labels" / "nms_n"], final_detections())"""
         self.backbone, self.head, self.voxel_size = backbone, head, voxel_size
+        self.nms, self._nms_state = check_nms_setting(nms), {}
         self.device = torch.device(device)
         self.margin = margin
         self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
@@ -257,7 +314,7 @@ class StaticNet:
         self.plan.begin_static()
         with P.using(self.plan), torch.no_grad():
             out = trace_net(self.plan, self.backbone, self.head, self.coords, self.feats, self.n_dev, self.voxel_size,
-                            self.device)
+                            self.device, nms=self.nms, nms_state=self._nms_state)
         self.plan.end_static()
         return out
 
@@ -284,6 +341,8 @@ class StaticNet:
         self.out["done"] = self.done
         return self.out
 
+    final_detections = staticmethod(final_detections)
+
 
 class StaticScene:
     """One scene forward as a replayable HIP graph: the whole launch sequence of forward_scene() (dense unprojection,
@@ -299,12 +358,16 @@ class StaticScene:
     assumptions -- non-zero means the scene outgrew the plan and must be re-run eagerly (forward_scene)."""
 
     def __init__(self, cfg, backbone, head, device, margin=1.2, dense=True, stream=None, by_reference=True,
-                 feature_dtype=torch.float32):
-        """feature_dtype: the ONE element type of this slot's feature maps.  torch.float32 (default): maps of any dtype are
+                 feature_dtype=torch.float32, nms=None):
+        """nms: None (default: the graph ends at the raw detections, exactly as without the argument) or
+        dict(score_thr=..., iou_thr=...): the per-class NMS of postprocess.nms is appended to the captured sequence (four launches,
+        same stream) and final_detections(out) returns boxes, scores and labels after the scene's one device->host read.
+        feature_dtype: the ONE element type of this slot's feature maps.  torch.float32 (default): maps of any dtype are
         converted, as ever.  torch.float16 / torch.bfloat16 (NeuS mode, C % 8 == 0): the trace reads 16-bit maps -- in place when
         they are channels-last in memory, through the 16-bit layout pass into a buffer of half the size otherwise -- and run()
         with maps of another dtype raises ValueError (rounding fp32 maps to 16 bits silently is not a hand-off)."""
         self.cfg, self.backbone, self.head = cfg, backbone, head
+        self.nms, self._nms_state = check_nms_setting(nms), {}
         self.feature_dtype = feature_dtype
         if feature_dtype != torch.float32:
             if feature_dtype not in rma.ELEM_CODES:
@@ -466,7 +529,7 @@ class StaticScene:
                 defer_feats=DEFER_POINT_FEATURES, feat_dtype=self.feature_dtype)
             moved = coords + self.offset_dev     # ray_marching.py:364 (one fp32 add per coordinate, as the reference)
             out.update(trace_net(plan, self.backbone, self.head, moved, feats, n_sel, cfg.voxel_size_fcaf3d, self.device,
-                                 extra_counts=[info["M"], n_sel], late=info))
+                                 extra_counts=[info["M"], n_sel], late=info, nms=self.nms, nms_state=self._nms_state))
             if not fixed:
                 self.seed_dev.add_(1)            # the next replay draws a fresh point subset
             if side is not None:
@@ -602,6 +665,8 @@ class StaticScene:
         if ne == 2:
             info.update(M=counts[0], M_selected=counts[1])
         return out["bboxes"].index_select(0, rows), out["scores"].index_select(0, rows), info
+
+    final_detections = staticmethod(final_detections)
 
     def detect(self, features_nchw, projections, tsdf, rebuild_after=4, offset=None, by_reference=None):
         """run() + detections() with the fallback a server wants: a scene that outgrows the size plan (status != 0) is

@@ -2,6 +2,8 @@
 and the indoor mAP evaluation.  Host mirror of the reference's post_process/nms_bbox.py:17-66 and
 post_process/evaluate_bbox.py:18-100 (which call mmdet3d's pcdet_nms_* and indoor_eval -- third-party, semantics
 restated in include/cnrma.h / oracle/post_oracle.py)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -64,6 +66,70 @@ def nms(bboxes, scores, score_thr=0.01, iou_thr=0.5):
     if not out_b:
         return bboxes.new_zeros((0, bboxes.shape[1])), bboxes.new_zeros((0,)), bboxes.new_zeros((0,), dtype=torch.long)
     return torch.cat(out_b), torch.cat(out_s), torch.cat(out_l)
+
+
+NMS_DEVICE_MAX_ROWS = 4096          # cnrma_nms_classes_f32: 64 lanes x 64 bits, one wave scans a class
+
+
+def nms_device_buffers(n_cap, n_cls, cols, device, out_cap=None):
+    """workspace and outputs of one nms_device() call site (a static trace allocates them once and hands them in as `out=`);
+    out_cap defaults to n_cap * n_cls, which no input overflows"""
+    out_cap = n_cap * n_cls if out_cap is None else int(out_cap)
+    need = _lib.load().cnrma_nms_classes_workspace_bytes(n_cap, n_cls)
+    return dict(workspace=torch.empty(max(need, 16), dtype=torch.uint8, device=device),
+                boxes=torch.zeros((out_cap, cols), dtype=torch.float32, device=device),
+                scores=torch.zeros((out_cap,), dtype=torch.float32, device=device),
+                labels=torch.zeros((out_cap,), dtype=torch.long, device=device),
+                n_out=torch.zeros(1, dtype=torch.int32, device=device))
+
+
+def _live_rows(bboxes, scores, valid, sizes):
+    """the live rows of a padded block, compacted (one device->host read)"""
+    if valid is None:
+        return bboxes, scores
+    rows, r0 = [], 0
+    for k, v in zip(sizes, _lib.read_ints(valid)):
+        rows.append(torch.arange(r0, r0 + min(max(v, 0), k), device=bboxes.device))
+        r0 += k
+    rows = torch.cat(rows)
+    return bboxes.index_select(0, rows), scores.index_select(0, rows)
+
+
+def nms_device(bboxes, scores, score_thr=0.01, iou_thr=0.5, valid=None, sizes=None, padded=False, out=None, out_cap=None):
+    """nms() for all classes at once on the device (cnrma_nms_classes_f32: rank, mask, scan, gather -- four launches, nothing
+    read back in between); every suppression decision is that of nms().
+    bboxes [n, 6|7], scores [n, n_cls] float32.  A padded block -- what the static trace makes -- is described by `sizes`
+    (static segment lengths, sum = n) and `valid` (device int32 [len(sizes)]: live rows at the head of each segment); dead rows
+    may hold anything.  valid=None: every row is live.
+    Returns the triple of nms() after ONE device->host read (the count).  padded=True: no read at all -- the capacity-sized
+    (boxes [out_cap, 6|7], scores [out_cap], labels [out_cap]) and n_out (device int32 [1], the true total even beyond out_cap;
+    rows behind it are undefined); capturable.  `out`: buffers of nms_device_buffers() to write into instead of fresh ones.
+    More than NMS_DEVICE_MAX_ROWS rows (or tensors that are not float32) go through nms(), which then reads back as ever."""
+    _lib.require_gpu()
+    n, n_cls = scores.shape
+    cols = bboxes.shape[1]
+    sizes = [n] if sizes is None else [int(k) for k in sizes]
+    if sum(sizes) != n or bboxes.shape[0] != n or not 1 <= len(sizes) <= 8:
+        raise ValueError(f"sizes {sizes} (1 to 8 segments) must add up to the {n} rows of bboxes and scores")
+    if n > NMS_DEVICE_MAX_ROWS or bboxes.dtype != torch.float32 or scores.dtype != torch.float32 or n_cls == 0:
+        if padded:
+            raise _lib.CnrmaError(f"the device NMS takes float32 blocks of at most {NMS_DEVICE_MAX_ROWS} rows (got {n})")
+        return nms(*_live_rows(bboxes, scores, valid, sizes), score_thr=score_thr, iou_thr=iou_thr)
+    bboxes, scores = bboxes.contiguous(), scores.contiguous()
+    if out is None:
+        out = nms_device_buffers(n, n_cls, cols, bboxes.device, out_cap)
+    if valid is not None:
+        valid = valid.to(torch.int32).contiguous()
+        assert valid.numel() == len(sizes)
+    ws = out["workspace"]
+    host_sizes = (ctypes.c_int32 * len(sizes))(*sizes)
+    call("cnrma_nms_classes_f32", ptr(bboxes), cols, ptr(scores), n, n_cls, ctypes.addressof(host_sizes), len(sizes),
+         ptr(valid), float(score_thr), float(iou_thr), ptr(ws), ws.numel(), ptr(out["boxes"]), ptr(out["scores"]),
+         ptr(out["labels"]), out["boxes"].shape[0], ptr(out["n_out"]), stream())
+    if padded:
+        return out["boxes"], out["scores"], out["labels"], out["n_out"]
+    k = min(_lib.read_ints(out["n_out"])[0], out["boxes"].shape[0])
+    return out["boxes"][:k], out["scores"][:k], out["labels"][:k]
 
 
 def to_saved_layout(boxes):

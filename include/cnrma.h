@@ -722,6 +722,29 @@ int cnrma_fcaf3d_scores_f32(const float* cls, const float* centerness, int64_t n
 int cnrma_nms_mask_f32(const float* boxes_sorted, int n, float iou_thr, int rotated, uint64_t* mask, void* stream);
 int cnrma_box_iou_f32(const float* a, int na, const float* b, int nb, int rotated, int mode3d, float* iou, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * Per-class 3D NMS of a whole scene on the device   replaces the class loop of post_process/nms_bbox.py:17-58 and the head's
+ * own _nms (fcaf3d_head.py:351-392): for every class the rows with score > score_thr, in descending score order (ties: the lower
+ * row first), greedy BEV NMS with the suppression test of cnrma_nms_mask_f32 (IoU > iou_thr; box_cols = 7: rotated, 6: axis-aligned).
+ * Four launches whatever the data and the class count (rank, mask, scan, gather); no device->host read, no allocation, no
+ * synchronisation: capturable in a graph.
+ * Input: the padded detection block of the static trace -- boxes [n_cap][box_cols], scores [n_cap][n_cls], n_segments (1..8)
+ *   segments of sizes[l] rows (HOST array, sum = n_cap) of which the first valid[l] are live (valid: DEVICE int32 [n_segments],
+ *   NULL = every row is live).  Dead rows may hold anything (NaN included) and are never read as candidates.
+ *   n_cap <= 4096 (64 lanes x 64 bits: one wave scans a class); anything larger returns CNRMA_EINVAL.
+ * Output: out_boxes [out_cap][box_cols], out_scores [out_cap], out_labels int64 [out_cap] -- classes ascending, descending score
+ *   inside a class --, n_out[0] = the number of detections (the TRUE total even when it exceeds out_cap; rows from out_cap on
+ *   are dropped, rows behind n_out are left as they were).
+ * workspace: cnrma_nms_classes_workspace_bytes(n_cap, n_cls) bytes, 16-byte aligned (dominated by the bit masks:
+ *   n_cls x n_cap x ceil(n_cap / 64) x 8 bytes; it is not cleared -- the scan reads only words the mask kernel wrote).
+ *   The size is 0 for arguments the entry point rejects.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t cnrma_nms_classes_workspace_bytes(int n_cap, int n_cls);
+int cnrma_nms_classes_f32(const float* boxes, int box_cols, const float* scores, int n_cap, int n_cls, const int32_t* sizes,
+                          int n_segments, const int32_t* valid, float score_thr, float iou_thr, void* workspace,
+                          size_t workspace_bytes, float* out_boxes, float* out_scores, int64_t* out_labels, int out_cap,
+                          int32_t* n_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,8 @@ from cnrma_amd import postprocess  # noqa: E402
 def nms_bboxes(args):
     for scene_id in sorted(os.listdir(args.result_path)):
         raw = np.load(os.path.join(args.result_path, scene_id, scene_id + "_bbox_raw.npz"))
-        boxes, scores, labels = postprocess.nms(torch.tensor(raw["bboxes"]).cuda(), torch.tensor(raw["scores"]).cuda())
+        # all classes in one pass on the device (scenes of at most 4096 rows; larger ones take the class-by-class path inside)
+        boxes, scores, labels = postprocess.nms_device(torch.tensor(raw["bboxes"]).cuda(), torch.tensor(raw["scores"]).cuda())
         np.savez(os.path.join(args.result_path, scene_id, scene_id + args.postfix),
                  boxes=postprocess.to_saved_layout(boxes).cpu().numpy(), scores=scores.cpu().numpy(),
                  labels=labels.cpu().numpy())

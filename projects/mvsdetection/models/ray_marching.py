@@ -60,7 +60,7 @@ class RayMarching(MultiViewBase):
                  train_cfg=None, test_cfg=None, pretrained=None, use_feature_transform=True,
                  ray_marching_type="neus", depth_points=None, neus_threshold=None, middle_save_path=None,
                  middle_visualize_path=None, point_sampler="device", static_test=True, static_slots=3, static_calibration=2,
-                 static_feature_handoff="reference", static_feature_dtype="float32"):
+                 static_feature_handoff="reference", static_feature_dtype="float32", static_nms=None):
         super().__init__(pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin, backbone2d_stride,
                          backbone2d, feature_2d, backbone_3d, tsdf_head, save_path)
         self.detection_backbone = build_backbone(detection_backbone)
@@ -108,6 +108,11 @@ class RayMarching(MultiViewBase):
         if static_feature_dtype not in ("float32", "keep"):
             raise ValueError(f"static_feature_dtype must be 'float32' or 'keep', got {static_feature_dtype!r}")
         self.static_feature_dtype = static_feature_dtype
+        # static_nms: None (default: the scene graphs end at the raw detections) or dict(score_thr=..., iou_thr=...): the per-class
+        # NMS of post_process/nms_bbox.py runs at the end of every scene graph and the writer thread puts {scene}_atlas_bbox.npz
+        # (boxes, scores, labels: the file nms_bbox.py writes) next to {scene}_bbox_raw.npz
+        from cnrma_amd import pipeline as _pipeline
+        self.static_nms = _pipeline.check_nms_setting(static_nms)
         self._static = {}
         self._writer = None
         import atexit
@@ -389,7 +394,7 @@ class RayMarching(MultiViewBase):
                                        self.max_points, self.voxel_size_fcaf3d, self.ray_marching_type, self.depth_points, "device")
             first = pipeline.StaticScene(cfg, self.detection_backbone, self.detection_head, feats.device, margin=self.static_margin,
                                          dense=dense_in_graph, by_reference=self.static_feature_handoff == "reference",
-                                         feature_dtype=fdt)
+                                         feature_dtype=fdt, nms=self.static_nms)
             ctx = dict(cfg=cfg, slots=[first], pending=[None] * max(1, self.static_slots), seen=0, k=0, built=False,
                        weights=pipeline.weight_tensors(self.detection_backbone, self.detection_head), tag=None, grown=0)
             self._static[key] = ctx
@@ -397,6 +402,7 @@ class RayMarching(MultiViewBase):
             # calibration scenes: the eager path produces their results (files, module state) exactly as before; a second,
             # recording pass over the same inputs sizes the graphs (its detections are dropped)
             self._run(inputs, test=True)
+            self._save_final(*self.last_detections[0], scene)
             tsdf = self._last_tsdf.reshape(tuple(self.voxel_dim))
             first = ctx["slots"][0]
             first.calibrate(feats, proj, tsdf, offset=offset)
@@ -450,7 +456,8 @@ class RayMarching(MultiViewBase):
         ctx["slots"] = [first]
         for _ in range(1, max(1, self.static_slots)):
             st = pipeline.StaticScene(ctx["cfg"], self.detection_backbone, self.detection_head, feats.device, margin=first.margin,
-                                      dense=dense_in_graph, by_reference=first.by_reference, feature_dtype=first.feature_dtype)
+                                      dense=dense_in_graph, by_reference=first.by_reference, feature_dtype=first.feature_dtype,
+                                      nms=first.nms)
             st.build(feats, proj, tsdf, plan=first.plan)
             ctx["slots"].append(st)
         ctx["built"], ctx["grown"] = True, 0
@@ -494,9 +501,14 @@ class RayMarching(MultiViewBase):
                 with torch.cuda.stream(stream), torch.no_grad():
                     b, s, _ = pipeline.StaticScene.detections(out)
                     b, s = b.cpu(), s.cpu()
+                    final = None
+                    if "nms_n" in out:                           # static_nms: the graph ended with the per-class NMS
+                        final = [t.cpu().numpy() for t in pipeline.StaticScene.final_detections(out)]
                 model = ref()
                 if model is not None:
                     model._write_raw(b.numpy(), s.numpy(), item["scene"])
+                    if final is not None:
+                        model._write_final(*final, item["scene"])
                 item["result"], item["status"] = (b, s), "ok"
             except _lib.CnrmaError:
                 item["status"] = "violation"                     # outgrew the size plan: the main thread re-runs it eagerly
@@ -507,7 +519,7 @@ class RayMarching(MultiViewBase):
                 # nothing of a finished scene -- its static buffers, the detector itself -- may outlive it in this frame: the
                 # thread blocks in q.get() between scenes, and a name still bound here kept the last detector and its graphs
                 # (tens of GB at the north-star shape) alive after `del model` (round 6: bench.py's resident memory)
-                item = out = model = b = s = None
+                item = out = model = b = s = final = None
 
     def _drain(self, ctx, i):
         """the slot's previous scene has left its static buffers (its file is written) -- or, if it outgrew the size plan,
@@ -571,9 +583,27 @@ class RayMarching(MultiViewBase):
             np.savez(tmp, bboxes=bboxes, scores=scores)          # fcaf3d_head.py:266-271; renamed into place: a reader (or a crash)
             os.replace(tmp, final)                               # never sees a half-written file
 
+    def _write_final(self, boxes, scores, labels, scene):
+        """{scene}_atlas_bbox.npz as post_process/nms_bbox.py writes it (static_nms)"""
+        if self.save_path is not None and scene is not None:
+            d = os.path.join(self.save_path, scene)
+            os.makedirs(d, exist_ok=True)
+            final = os.path.join(d, scene + "_atlas_bbox.npz")
+            tmp = final + f".tmp{os.getpid()}.npz"
+            np.savez(tmp, boxes=boxes, scores=scores, labels=labels)
+            os.replace(tmp, final)
+
     def _save_raw(self, bboxes, scores, scene):
         self.last_detections = [(bboxes, scores)]
         self._write_raw(bboxes.detach().cpu().numpy(), scores.detach().cpu().numpy(), scene)
+        self._save_final(bboxes, scores, scene)
+
+    def _save_final(self, bboxes, scores, scene):
+        """static_nms for a scene that did not run as a graph (calibration scenes, scenes that outgrew the plan): the same file"""
+        if self.static_nms is not None and self.save_path is not None and scene is not None:
+            from cnrma_amd import postprocess
+            final = postprocess.nms_device(bboxes.detach(), scores.detach(), **self.static_nms)
+            self._write_final(*[t.cpu().numpy() for t in final], scene)
 
     def save_middle_result(self, scene_id, coords, offset, save_path, visualize_path=None):
         """dump the aggregated points of a scene ([M, 3 + C], coordinates moved by `offset`, at most max_points rows drawn
