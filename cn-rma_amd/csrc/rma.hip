@@ -219,15 +219,36 @@ __device__ __forceinline__ float div_by_vs(float a, float vs, float y) {
 
 struct TabSample { float s; bool valid; int rad; };
 
-// Free-space skipping (round 5).  skip[block] (one byte per 4 x 4 x 4 block of voxels, cnrma_rma_march_tables_f32) = R in {0, 4, 8,
-// 12, 16}: every voxel within Chebyshev distance R of ANY voxel of the block holds the block's table value, bit for bit.  A
+// Free-space skipping.  far[block] (one byte per 4 x 4 x 4 block of voxels, cnrma_rma_march_tables_f32) = R = min(4 r, 252): every
+// voxel within Chebyshev distance R of ANY voxel of the block holds the block's table value, bit for bit (r = the block's Chebyshev
+// distance, in blocks, to the nearest block that is mixed, partial, on the grid's border or next to a block of another value).  A
 // sample whose successor has the same table value is a no-op of the march (alpha = 0, w = 0 < thr, transmittance x 1.0: the
 // `still` test below), so a ray standing in a voxel of radius R may jump over the next j steps without evaluating them
 // whenever they are certain to land inside that radius: the rounded voxel index moves by at most |delta| + 1 per axis for a
 // displacement of delta voxels, the displacement of j steps is j * m with m = t_one * max|d_axis| / vs, so j < (R - 1) / m
-// suffices (taken with a margin of 1 % + 0.01 voxel; the fp32 error of the positions is ~1e-5 voxel).  The records and sums
-// are those of the step-by-step march, bit for bit (tests: golden vectors, oracle, skip on / off).
-constexpr int SKIP_B = 4, SKIP_RMAX = 16;
+// suffices (taken with a margin of 1 % + 0.01 voxel).  The argument does not depend on the size of R, and neither does the
+// margin: a position is o + d * (n * t_one), three roundings whatever the step, so its fp32 error grows with t (a few ulp of a
+// coordinate of some metres: ~1e-5 voxel), not with the length j of the jump that led there; the real displacement of a jump
+// of 60 steps is 60 m exactly, and the 1 % taken off it (0.6 voxel there) only grows with j.  j itself comes out of one fp32
+// product whose relative error (~1e-7) is far inside the 1 %.  The records and sums are those of the step-by-step march, bit
+// for bit (tests: golden vectors, oracle, skip on / off).
+//
+// Layout of the skip buffer (cnrma_rma_skip_table_bytes), nb = number of blocks, every region starting at a multiple of 256 bytes:
+//   [0, nb)                 min(far, 16): the radii of the former 16-voxel cap (kept for readers of the buffer's head)
+//   [a(nb), a(nb) + 4 nb)   block values (scratch of the build), a(n) = n rounded up to 256
+//   [F, F + nb)             far, what the march reads; F = a(nb) + a(4 nb)
+//   [F + a(nb), F + 3 a(nb)) two byte planes of the distance transform (scratch of the build)
+constexpr int SKIP_B = 4, SKIP_RMAX = 16, SKIP_FAR_MAX = 252;
+#ifndef CNRMA_SKIP_JMIN
+#define CNRMA_SKIP_JMIN 3
+#endif
+constexpr int SKIP_JMIN = CNRMA_SKIP_JMIN;      // shortest jump worth taking (a jump costs one look-up, like a plain no-op step)
+
+__host__ __device__ __forceinline__ int64_t skip_align(int64_t n) { return (n + 255) & ~(int64_t)255; }
+__host__ __device__ __forceinline__ int64_t skip_blocks(int X, int Y, int Z) {
+  return (int64_t)((X + SKIP_B - 1) / SKIP_B) * ((Y + SKIP_B - 1) / SKIP_B) * ((Z + SKIP_B - 1) / SKIP_B);
+}
+__host__ __device__ __forceinline__ int64_t skip_far_offset(int64_t nb) { return skip_align(nb) + skip_align(4 * nb); }
 
 __device__ __forceinline__ TabSample fetch_step(const Ray& r, int n, const MarchParams& p, float inv_vs,
                                                 const float* __restrict__ tab, float s_out,
@@ -280,30 +301,40 @@ __device__ __forceinline__ void neus_march_block(const MarchParams& p, const flo
     // steps a jump may cover per unit of safe radius (see SKIP_B above): j <= (R - 1.01) / (1.01 m)
     const float m_vox = p.t_one * fmaxf(fmaxf(fabsf(ray.dx), fabsf(ray.dy)), fabsf(ray.dz)) * inv_vs * 1.01f;
     const float per_vox = m_vox > 1e-6f ? 1.0f / m_vox : 0.0f;
-    TabSample cur = fetch_step(ray, a, p, inv_vs, tab, s_out, skip, by, bz);
+    const uint8_t* far = skip != nullptr ? skip + skip_far_offset(skip_blocks(p.X, p.Y, p.Z)) : nullptr;
+    TabSample cur = fetch_step(ray, a, p, inv_vs, tab, s_out, far, by, bz);
     TabSample n1 = cur, n2 = cur;                       // samples a+1, a+2 (only used when inside [a, b])
-    if (a + 1 <= b) n1 = fetch_step(ray, a + 1, p, inv_vs, tab, s_out, skip, by, bz);
+    if (a + 1 <= b) n1 = fetch_step(ray, a + 1, p, inv_vs, tab, s_out, far, by, bz);
     // a step whose successor has the same table value has alpha = max((s - s) / s, 0) = 0: w = 0 < thr (nothing kept) and
     // the transmittance is multiplied by 1.0 -- the whole body is a no-op (given 0 < thr <= 1, so that neither "w >= thr"
     // nor the exit test can change).  Rays spend most of their steps in free space (tsdf == -1: one table value); when every
     // lane of a wave is in such a step the division, the fp64 product and the bookkeeping are skipped (-25 of ~85 VALU
     // instructions per step; the kernel is VALU-issue bound).
     const bool can_skip = p.thr > 0.0f && p.thr <= 1.0f;
+    // landed: cur is the sample a jump landed on, fetched by the jump itself (so it brings its own radius) and n1 is not fetched
+    // yet.  Such a sample holds the value of the sample the jump started from, which passed the `still` test (so it is no NaN:
+    // NaN == NaN is false); if its own radius allows a jump of j >= 1 steps, sample n + 1 holds that value too, i.e. `still` is
+    // known to be true without n1 -- jumps chain at ONE look-up each.  (Before: two per jump, the landing sample's successor
+    // and the plain step that followed every jump to learn a radius again.)
+    bool landed = false;
     for (int n = a; n <= b; ++n) {
-      const bool still = can_skip && (n + 1 <= b) && (n1.s == cur.s);
-      if (still && cur.rad > 0) {
-        // every step up to n + j lands in a voxel holding cur.s: steps n .. n + j - 1 are no-ops; go on at n + j with the same
-        // sample value (its own radius is not known: one plain step follows before the next jump)
+      if (can_skip && cur.rad > 0) {
+        // every step up to n + j lands in a voxel holding cur.s: steps n .. n + j - 1 are no-ops; go on at n + j
         int j = (int)(((float)cur.rad - 1.01f) * per_vox);
         j = min(j, b - 2 - n);
-        if (j >= 3) {
+        if (j >= SKIP_JMIN && (landed || n1.s == cur.s)) {                      // j >= 1: n + 1 <= b
           n += j - 1;                                                           // the loop's ++n lands on n + j
-          cur.rad = 0;
-          n1 = fetch_step(ray, n + 2, p, inv_vs, tab, s_out, skip, by, bz);     // sample (n + j) + 1
+          cur = fetch_step(ray, n + 1, p, inv_vs, tab, s_out, far, by, bz);     // the landing sample itself: value and radius
+          landed = true;
           continue;
         }
       }
-      if (n + 2 <= b) n2 = fetch_step(ray, n + 2, p, inv_vs, tab, s_out, skip, by, bz);     // in flight during this step
+      if (landed) {                                                             // the chain ends here (n <= b - 2): a plain step
+        n1 = fetch_step(ray, n + 1, p, inv_vs, tab, s_out, far, by, bz);
+        landed = false;
+      }
+      const bool still = can_skip && (n + 1 <= b) && (n1.s == cur.s);
+      if (n + 2 <= b) n2 = fetch_step(ray, n + 2, p, inv_vs, tab, s_out, far, by, bz);      // in flight during this step
       if (!still) {
         float s_next;
         if (n + 1 <= b) s_next = n1.s;
@@ -415,34 +446,50 @@ __global__ __launch_bounds__(256) void skip_blockval_kernel(const float* __restr
   }
   blockval[b] = v;
 }
-// pass 2: skip[b] = 4 r for the largest r <= 4 such that every block within Chebyshev distance r of b exists and holds b's value
-__global__ __launch_bounds__(256) void skip_radius_kernel(const uint32_t* __restrict__ blockval, int bx, int by, int bz,
-                                                          uint8_t* __restrict__ skip) {
+// pass 2: is block b a boundary of its region?  It is when it has no value (mixed / partial), when it lies on the grid's border, or
+// when one of its 26 neighbours holds another value.  Every block within Chebyshev distance r of b exists and holds b's value
+// exactly when no boundary block lies within distance r - 1 of b (a block of another value at distance D makes one of its
+// neighbours at distance D - 1 a boundary, and nothing nearer is one), so the radius of b in blocks IS its Chebyshev distance to
+// the nearest boundary block.  dist[b] = 0 for a boundary block, 255 ("none seen yet") otherwise.
+__global__ __launch_bounds__(256) void skip_boundary_kernel(const uint32_t* __restrict__ blockval, int bx, int by, int bz,
+                                                            uint8_t* __restrict__ dist) {
   const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= (int64_t)bx * by * bz) return;
   const int kz = (int)(b % bz), ky = (int)((b / bz) % by), kx = (int)(b / ((int64_t)bz * by));
   const uint32_t v = blockval[b];
-  int r = 0;
-  if (v != 0xFFFFFFFFu) {
-    constexpr int RB = SKIP_RMAX / SKIP_B;
-    for (r = 0; r < RB; ++r) {                               // does the shell at distance r + 1 hold v everywhere?
-      const int d = r + 1;
-      if (kx - d < 0 || ky - d < 0 || kz - d < 0 || kx + d >= bx || ky + d >= by || kz + d >= bz) break;
-      bool ok = true;
-      for (int i = -d; i <= d && ok; ++i)
-        for (int j = -d; j <= d && ok; ++j) {
-          const bool face = i == -d || i == d || j == -d || j == d;
-          const uint32_t* q = blockval + ((int64_t)(kx + i) * by + (ky + j)) * bz + kz;
-          if (face) {
-            for (int k = -d; k <= d; ++k) ok = ok && q[k] == v;
-          } else {
-            ok = q[-d] == v && q[d] == v;
-          }
-        }
-      if (!ok) break;
-    }
+  bool inner = v != 0xFFFFFFFFu && kx > 0 && ky > 0 && kz > 0 && kx + 1 < bx && ky + 1 < by && kz + 1 < bz;
+  if (inner) {
+    for (int i = -1; i <= 1; ++i)
+      for (int j = -1; j <= 1; ++j) {
+        const uint32_t* q = blockval + ((int64_t)(kx + i) * by + (ky + j)) * bz + kz;
+        inner = inner && q[-1] == v && q[0] == v && q[1] == v;
+      }
   }
-  skip[b] = (uint8_t)(r * SKIP_B);
+  dist[b] = inner ? 255 : 0;
+}
+
+// passes 3-5: the Chebyshev distance transform, one axis per pass (z, y, x): out[b] = min over the blocks c of b's line along
+// the axis of max(|b - c|, in[c]).  min and max distribute (max(a, min f) = min max(a, f)), so after the three passes out[b] is the
+// minimum over ALL blocks c of max(|dx|, |dy|, |dz|, boundary(c) ? 0 : 255): the exact distance, capped at 255.  A candidate at
+// distance d >= the best so far cannot improve it, so a thread looks at 2 x (its result) neighbours.  The last pass (radii !=
+// NULL) writes the radii in voxels instead: far = min(4 d, 252) and the head of the buffer min(4 d, 16).
+__global__ __launch_bounds__(256) void skip_distance_pass_kernel(const uint8_t* __restrict__ in, int64_t nb, int n_axis,
+                                                                 int64_t stride, uint8_t* __restrict__ out,
+                                                                 uint8_t* __restrict__ radii) {
+  const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= nb) return;
+  const int k = (int)((b / stride) % n_axis);
+  int best = in[b];
+  for (int d = 1; d < best; ++d) {
+    if (k - d >= 0) best = min(best, max(d, (int)in[b - d * stride]));
+    if (k + d < n_axis) best = min(best, max(d, (int)in[b + d * stride]));
+  }
+  if (radii != nullptr) {
+    out[b] = (uint8_t)min(best * SKIP_B, SKIP_FAR_MAX);
+    radii[b] = (uint8_t)min(best * SKIP_B, SKIP_RMAX);
+  } else {
+    out[b] = (uint8_t)best;
+  }
 }
 
 // Emission from the kept-sample records, two small kernels:
@@ -738,8 +785,8 @@ extern "C" int cnrma_rma_sigmoid_table_f32(const float* tsdf, int64_t n, float* 
 }
 
 extern "C" size_t cnrma_rma_skip_table_bytes(int X, int Y, int Z) {
-  const size_t nb = (size_t)ceil_div(X, SKIP_B) * (size_t)ceil_div(Y, SKIP_B) * (size_t)ceil_div(Z, SKIP_B);
-  return ((nb + 255) & ~(size_t)255) + nb * sizeof(uint32_t);               // radii, then the pass-1 scratch
+  const int64_t nb = skip_blocks(X, Y, Z);
+  return (size_t)(skip_far_offset(nb) + 3 * skip_align(nb));                // layout: see SKIP_B
 }
 
 extern "C" int cnrma_rma_march_tables_f32(const float* tsdf, int X, int Y, int Z, float* table, void* skip_table, void* stream) {
@@ -751,11 +798,18 @@ extern "C" int cnrma_rma_march_tables_f32(const float* tsdf, int X, int Y, int Z
   hipLaunchKernelGGL(sigmoid_table_kernel, dim3((unsigned)blocks), dim3(256), 0, st, tsdf, n, table);
   if (skip_table != nullptr) {
     const int bx = (int)ceil_div(X, SKIP_B), by = (int)ceil_div(Y, SKIP_B), bz = (int)ceil_div(Z, SKIP_B);
-    const int64_t nb = (int64_t)bx * by * bz;
+    const int64_t nb = skip_blocks(X, Y, Z);
     uint8_t* skip = reinterpret_cast<uint8_t*>(skip_table);
-    uint32_t* blockval = reinterpret_cast<uint32_t*>(skip + ((nb + 255) & ~(int64_t)255));
-    hipLaunchKernelGGL(skip_blockval_kernel, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, st, table, X, Y, Z, bx, by, bz, blockval);
-    hipLaunchKernelGGL(skip_radius_kernel, dim3((unsigned)ceil_div(nb, 256)), dim3(256), 0, st, blockval, bx, by, bz, skip);
+    uint32_t* blockval = reinterpret_cast<uint32_t*>(skip + skip_align(nb));
+    uint8_t* far = skip + skip_far_offset(nb);
+    uint8_t* d0 = far + skip_align(nb);
+    uint8_t* d1 = d0 + skip_align(nb);
+    const dim3 grid((unsigned)ceil_div(nb, 256)), block(256);
+    hipLaunchKernelGGL(skip_blockval_kernel, grid, block, 0, st, table, X, Y, Z, bx, by, bz, blockval);
+    hipLaunchKernelGGL(skip_boundary_kernel, grid, block, 0, st, blockval, bx, by, bz, d0);
+    hipLaunchKernelGGL(skip_distance_pass_kernel, grid, block, 0, st, d0, nb, bz, (int64_t)1, d1, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(skip_distance_pass_kernel, grid, block, 0, st, d1, nb, by, (int64_t)bz, d0, (uint8_t*)nullptr);
+    hipLaunchKernelGGL(skip_distance_pass_kernel, grid, block, 0, st, d0, nb, bx, (int64_t)by * bz, far, skip);
   }
   CNRMA_LAUNCH_CHECK();
   return 0;

@@ -33,23 +33,56 @@ extern "C" int cnrma_range_violations_i32(const int32_t* values, const int32_t* 
 namespace {
 
 constexpr int SCAN_BLOCK = 256;
-constexpr int SCAN_ITEMS = 8;                       // items per thread
-constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;  // 2048 items per block
+constexpr int SCAN_VECS = 4;                        // 4-item vectors per thread
+constexpr int SCAN_ITEMS = 4 * SCAN_VECS;           // items per thread
+constexpr int SCAN_TILE = SCAN_BLOCK * SCAN_ITEMS;  // 4096 items per block
+constexpr int SCAN_WAVE_ITEMS = 64 * SCAN_ITEMS;    // a wave owns 1024 consecutive items of the tile
 
 template <typename T>
 __device__ __forceinline__ int scan_load(const T* in, int64_t i, int64_t n) {
   return i < n ? (int)in[i] : 0;
 }
 
+// Items -> lanes.  A wave owns SCAN_WAVE_ITEMS consecutive items as SCAN_VECS rows of 64 vectors of 4 items; lane l holds vector l
+// of every row.  A row is then ONE contiguous 1-KiB piece of the output (256 B of a byte mask) that the wave reads and writes with
+// one 16-byte (4-byte) access per lane -- a thread owning 16 consecutive items would touch memory at a lane stride of 64 bytes,
+// 16 cache lines per wave instruction.  `wide`: the tile is full and the pointers are aligned (uniform over the block); the
+// last, partial tile and misaligned buffers take the guarded scalar accesses on the same item -> lane map.
+__device__ __forceinline__ int64_t scan_vec_base(int64_t tile_base, int k) {
+  return tile_base + (int64_t)(threadIdx.x >> 6) * SCAN_WAVE_ITEMS + (int64_t)(k * 64 + (threadIdx.x & 63)) * 4;
+}
+
+template <typename T>
+__device__ __forceinline__ void scan_load_vec(const T* __restrict__ in, int64_t i, int64_t n, bool wide, int v[4]) {
+  static_assert(sizeof(T) == 4 || sizeof(T) == 1, "int32 items or byte masks");
+  if (wide) {
+    if constexpr (sizeof(T) == 4) {
+      const int4 q = *reinterpret_cast<const int4*>(in + i);
+      v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w;
+    } else {
+      const uint32_t q = *reinterpret_cast<const uint32_t*>(in + i);
+      v[0] = (int)(q & 255u); v[1] = (int)((q >> 8) & 255u); v[2] = (int)((q >> 16) & 255u); v[3] = (int)(q >> 24);
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = scan_load(in, i + j, n);
+  }
+}
+
 // phase A: per-tile sums
 template <typename T>
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_tile_sums(const T* __restrict__ in, int32_t* __restrict__ tile_sum,
-                                                             int64_t n) {
+                                                             int64_t n, int aligned) {
   __shared__ int smem[SCAN_BLOCK / 64 + 1];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+  const int64_t tile_base = (int64_t)blockIdx.x * SCAN_TILE;
+  const bool wide = aligned != 0 && tile_base + SCAN_TILE <= n;
   int s = 0;
 #pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) s += scan_load(in, base + j, n);
+  for (int k = 0; k < SCAN_VECS; ++k) {
+    int v[4];
+    scan_load_vec(in, scan_vec_base(tile_base, k), n, wide, v);
+    s += (v[0] + v[1]) + (v[2] + v[3]);
+  }
   int total;
   block_excl_scan<SCAN_BLOCK>(s, smem, &total);
   if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
@@ -77,41 +110,62 @@ __global__ __launch_bounds__(1024) void scan_tile_offsets(int32_t* __restrict__ 
 
 // phase C: rescan each tile with its offset.  MODE 0: out[i] = exclusive sum (and out[n] = total);
 // MODE 1 (mask -> index): out[i] = in[i] ? rank : -1, n_sel[0] = total.
-// OWN_OFFSET (n_tiles <= SCAN_TILE, i.e. up to 4 M items): there is no phase B -- every block adds up the sums of the tiles
-// in front of it itself (<= 8 KB from L2), block 0 the grand total as well: two launches per scan instead of three.
+// OWN_OFFSET (n_tiles <= SCAN_TILE, i.e. up to 16.7 M items, the north-star shape's 12.3 M rays included): there is no phase B --
+// every block adds up the sums of the tiles in front of it itself (<= 16 KB from L2), block 0 the grand total as well: two launches per scan instead of three.
 template <typename T, int MODE, bool OWN_OFFSET>
 __global__ __launch_bounds__(SCAN_BLOCK) void scan_apply(const T* __restrict__ in, const int32_t* __restrict__ tile_off,
                                                          int32_t* __restrict__ out, int32_t* __restrict__ total_out,
-                                                         int64_t n, int64_t n_tiles) {
+                                                         int64_t n, int64_t n_tiles, int aligned) {
   __shared__ int smem[SCAN_BLOCK / 64 + 1];
-  const int64_t base = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
-  int v[SCAN_ITEMS];
-  int s = 0;
+  __shared__ int wave_sum[SCAN_BLOCK / 64];
+  const int64_t tile_base = (int64_t)blockIdx.x * SCAN_TILE;
+  const bool wide = aligned != 0 && tile_base + SCAN_TILE <= n;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int v[SCAN_VECS][4];
+  int ex[SCAN_VECS];                    // exclusive prefix of vector (k, lane) inside the wave's items
+  int run = 0;                          // sum of the rows before row k
 #pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    v[j] = scan_load(in, base + j, n);
-    s += v[j];
+  for (int k = 0; k < SCAN_VECS; ++k) {
+    scan_load_vec(in, scan_vec_base(tile_base, k), n, wide, v[k]);
+    const int q = (v[k][0] + v[k][1]) + (v[k][2] + v[k][3]);
+    const int incl = wave_incl_scan(q);
+    ex[k] = run + incl - q;
+    run += __shfl(incl, 63, 64);
   }
+  if (lane == 0) wave_sum[wid] = run;
   int offset, grand = 0;
   if constexpr (OWN_OFFSET) {
     const int upto = blockIdx.x == 0 ? (int)n_tiles : (int)blockIdx.x;   // block 0 needs the total (its own offset is 0)
     int part = 0;
     for (int i = threadIdx.x; i < upto; i += SCAN_BLOCK) part += tile_off[i];
     int sum;
-    block_excl_scan<SCAN_BLOCK>(part, smem, &sum);
-    __syncthreads();                                                  // smem is reused below
+    block_excl_scan<SCAN_BLOCK>(part, smem, &sum);                     // its barriers also publish wave_sum
     offset = blockIdx.x == 0 ? 0 : sum;
     grand = sum;
   } else {
     offset = tile_off[blockIdx.x];
     if (blockIdx.x == 0) grand = tile_off[n_tiles];
+    __syncthreads();
   }
-  int total;
-  int run = block_excl_scan<SCAN_BLOCK>(s, smem, &total) + offset;
 #pragma unroll
-  for (int j = 0; j < SCAN_ITEMS; ++j) {
-    if (base + j < n) out[base + j] = (MODE == 0) ? run : (v[j] ? run : -1);
-    run += v[j];
+  for (int w = 0; w < SCAN_BLOCK / 64; ++w) offset += w < wid ? wave_sum[w] : 0;
+#pragma unroll
+  for (int k = 0; k < SCAN_VECS; ++k) {
+    const int64_t i = scan_vec_base(tile_base, k);
+    int r[4];
+    int at = offset + ex[k];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      r[j] = (MODE == 0) ? at : (v[k][j] ? at : -1);
+      at += v[k][j];
+    }
+    if (wide) {
+      *reinterpret_cast<int4*>(out + i) = make_int4(r[0], r[1], r[2], r[3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (i + j < n) out[i + j] = r[j];
+    }
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     if (MODE == 0) out[n] = grand;
@@ -153,14 +207,16 @@ int run_scan(const T* in, int32_t* out, int32_t* total_out, int64_t n, void* wor
   }
   int64_t n_tiles = ceil_div(n > 0 ? n : 1, SCAN_TILE);
   int32_t* tile = reinterpret_cast<int32_t*>(workspace);
-  hipLaunchKernelGGL((scan_tile_sums<T>), dim3((unsigned)n_tiles), dim3(SCAN_BLOCK), 0, st, in, tile, n);
+  // 16-byte accesses on full tiles need a 16-byte aligned output and an input aligned to one vector of items (16 / 4 bytes)
+  const int aligned = (reinterpret_cast<uintptr_t>(out) & 15) == 0 && (reinterpret_cast<uintptr_t>(in) & (4 * sizeof(T) - 1)) == 0;
+  hipLaunchKernelGGL((scan_tile_sums<T>), dim3((unsigned)n_tiles), dim3(SCAN_BLOCK), 0, st, in, tile, n, aligned);
   if (n_tiles <= SCAN_TILE) {
     hipLaunchKernelGGL((scan_apply<T, MODE, true>), dim3((unsigned)n_tiles), dim3(SCAN_BLOCK), 0, st, in, tile, out, total_out,
-                       n, n_tiles);
+                       n, n_tiles, aligned);
   } else {
     hipLaunchKernelGGL(scan_tile_offsets, dim3(1), dim3(1024), 0, st, tile, n_tiles);
     hipLaunchKernelGGL((scan_apply<T, MODE, false>), dim3((unsigned)n_tiles), dim3(SCAN_BLOCK), 0, st, in, tile, out, total_out,
-                       n, n_tiles);
+                       n, n_tiles, aligned);
   }
   CNRMA_LAUNCH_CHECK();
   return 0;

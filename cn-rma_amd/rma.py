@@ -22,9 +22,10 @@ from ._lib import call, ptr, stream
 
 SIGMOID_TABLE = True     # production march: table-driven kernel (False: the per-step sigmoid kernel, kept for A/B runs)
 MARCH_SKIP = "auto"      # free-space skipping in the table-driven march (cnrma_rma_march_tables_f32): "auto" = from MARCH_SKIP_MIN_RAYS rays
-                         # on (north-star shape, 12.3 M rays: 2.71 -> 1.26 ms with the table builds; ScanNet shape, 0.77 M rays on a
-                         # stride-4 grid of maps: 0.30 -> 0.39 ms, the two extra launches cost more than the skipped steps save:
-                         # profiles/r05_march_ab_*.log); True / False force it (A/B, parity tests)
+                         # on (north-star shape, 12.3 M rays: 2.87 -> 1.10 ms with the table builds; ScanNet shape, 0.77 M rays on a
+                         # stride-4 grid of maps: 0.308 -> 0.326 ms with the uncapped radii and the distance-transform build -- was 0.387
+                         # with the shell search --, the five extra launches still cost more than the skipped steps save:
+                         # profiles/r10_march_ab_*.log); True / False force it (A/B, parity tests)
 MARCH_SKIP_MIN_RAYS = 4_000_000
 
 

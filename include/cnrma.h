@@ -165,11 +165,18 @@ int cnrma_rma_neus_emit_f32(const float* proj_inv, const float* tsdf, const floa
  * the same value: bit-identical weights).  With sig_table == NULL the TSDF is read and the sigmoid evaluated per step. */
 int cnrma_rma_sigmoid_table_f32(const float* tsdf, int64_t n, float* table, void* stream);
 /* The march's per-scene tables in one call: the sigmoid table and (skip_table != NULL) the free-space skip table -- one byte per
- * 4 x 4 x 4 block of voxels = a radius R in {0, 4, .., 16} such that every voxel within Chebyshev distance R of any voxel of the
- * block holds the block's table value bit for bit.  Samples whose successor has the same table value are no-ops of the march
- * (ray_marching.py:759-767: alpha = 0, w = 0 < thr, transmittance x 1), so a ray standing in such a block jumps over the steps
- * that are certain to stay inside the radius without evaluating them: same records, same sums, fewer evaluated steps (rays spend
- * most of their steps in free space).  skip_table: cnrma_rma_skip_table_bytes(X, Y, Z) bytes (radii + scratch of the build). */
+ * 4 x 4 x 4 block of voxels = a radius R = min(4 r, 252) such that every voxel within Chebyshev distance R of any voxel of the
+ * block holds the block's table value bit for bit (r: the largest number of blocks such that every block within Chebyshev
+ * distance r exists, is a whole block inside the grid and holds the block's value; mixed and partial blocks have 0).  Samples
+ * whose successor has the same table value are no-ops of the march (ray_marching.py:759-767: alpha = 0, w = 0 < thr,
+ * transmittance x 1), so a ray standing in such a block jumps over the steps that are certain to stay inside the radius without
+ * evaluating them: same records, same sums, fewer evaluated steps (rays spend most of their steps in free space).
+ * skip_table: cnrma_rma_skip_table_bytes(X, Y, Z) bytes.  Layout, with nb = ceil(X/4) ceil(Y/4) ceil(Z/4) blocks in x-major order
+ * and a(n) = n rounded up to a multiple of 256:
+ *   [0, nb)                   min(R, 16), one byte per block
+ *   [a(nb), a(nb) + 4 nb)     scratch of the build (block values)
+ *   [F, F + nb)               R, one byte per block -- what the march reads; F = a(nb) + a(4 nb)
+ *   [F + a(nb), F + 3 a(nb))  scratch of the build (two planes of the distance transform) */
 size_t cnrma_rma_skip_table_bytes(int X, int Y, int Z);
 int cnrma_rma_march_tables_f32(const float* tsdf, int X, int Y, int Z, float* table, void* skip_table, void* stream);
 #ifdef CNRMA_EXPERIMENTS
