@@ -831,44 +831,6 @@ __global__ __launch_bounds__(256) void emit_features_kernel(const FT* feat, cons
 // bounds check and no select
 __host__ __device__ inline int conv_cout_padded(int Cout) { return (Cout + 127) & ~127; }
 
-// element t of a prepared weight image -> (offset k, output column co, input channel cin).  Image order per plane:
-// [K][Cin / 32][Cout_p][32] -- the 32-channel slice of ALL columns of one offset is contiguous (Cin % 32 == 0: the only
-// case the MFMA kernels take; other channel counts keep the plain [K][Cout_p][Cin] order and are never read)
-__device__ __forceinline__ void weight_image_coords(int64_t t, int Cin, int Cp, int* k, int* co, int* cin) {
-  if ((Cin & (BK - 1)) == 0) {
-    const int c32 = (int)(t & (BK - 1));
-    const int64_t q = t / BK;
-    *co = (int)(q % Cp);
-    const int64_t q2 = q / Cp;
-    const int ns = Cin / BK;
-    *cin = (int)(q2 % ns) * BK + c32;
-    *k = (int)(q2 / ns);
-  } else {
-    *cin = (int)(t % Cin);
-    const int64_t q = t / Cin;
-    *co = (int)(q % Cp);
-    *k = (int)(q / Cp);
-  }
-}
-
-// W fp32 [K][Cin][Cout] -> Wt fp16 [2 planes][K][Cin/32][Cout_p][32] scaled by f16_scale_for(*amax), + trailer float = *amax
-__global__ __launch_bounds__(256) void prep_weights_f16_kernel(const float* __restrict__ w, uint16_t* __restrict__ wt, int K,
-                                                               int Cin, int Cout, const float* __restrict__ amax) {
-  const int Cp = conv_cout_padded(Cout);
-  const int64_t total = (int64_t)K * Cin * Cp;
-  const float am = read_amax(amax);
-  const float sc = f16_scale_for(am);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(wt + 2 * total) = am;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    int cin, co, k;
-    weight_image_coords(t, Cin, Cp, &k, &co, &cin);
-    uint16_t hh, mm;
-    split2_f16(co < Cout ? w[((int64_t)k * Cin + cin) * Cout + co] * sc : 0.0f, hh, mm);
-    wt[t] = hh;
-    wt[total + t] = mm;
-  }
-}
-
 // fp32 [N][C] -> split companion [N+1][C/8][3][8] bf16 (+ the zero row at index n_cap); one lane per 8 channels
 __global__ __launch_bounds__(256) void split_features_kernel(const float* __restrict__ in, int64_t n_cap,
                                                              const int32_t* __restrict__ n_dev, int C,
@@ -890,50 +852,6 @@ __global__ __launch_bounds__(256) void split_features_kernel(const float* __rest
   q[0] = make_uint4(h0.x, h0.y, h1.x, h1.y);
   q[1] = make_uint4(m0.x, m0.y, m1.x, m1.y);
   q[2] = make_uint4(l0.x, l0.y, l1.x, l1.y);
-}
-
-// W fp32 [K][Cin][Cout] -> Wt bf16 [3 planes][K][Cin/32][Cout_p][32]
-__global__ __launch_bounds__(256) void prep_weights_kernel(const float* __restrict__ w, __bf16* __restrict__ wt, int K,
-                                                           int Cin, int Cout) {
-  const int Cp = conv_cout_padded(Cout);
-  const int64_t total = (int64_t)K * Cin * Cp;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    int cin, co, k;
-    weight_image_coords(t, Cin, Cp, &k, &co, &cin);
-    const float a = co < Cout ? w[((int64_t)k * Cin + cin) * Cout + co] : 0.0f;
-    uint16_t hh, mm, ll;
-    split3_trunc(a, hh, mm, ll);
-    uint16_t* o = reinterpret_cast<uint16_t*>(wt);
-    o[t] = hh;
-    o[total + t] = mm;
-    o[2 * total + t] = ll;
-  }
-}
-
-// W fp32 [K][Cin][Cout] -> Wt bf16 [K][Cin/32][Cout_p][32], round to nearest (MODE 2)
-__global__ __launch_bounds__(256) void prep_weights_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ wt, int K,
-                                                                int Cin, int Cout) {
-  const int Cp = conv_cout_padded(Cout);
-  const int64_t total = (int64_t)K * Cin * Cp;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    int cin, co, k;
-    weight_image_coords(t, Cin, Cp, &k, &co, &cin);
-    wt[t] = (__bf16)(co < Cout ? w[((int64_t)k * Cin + cin) * Cout + co] : 0.0f);
-  }
-}
-
-// the image of the TRANSPOSED weights for dgrad, straight from W: Wd[k] = W[flip ? K - 1 - k : k]^T ([Cout] -> [Cin]), bf16
-// [K][Cout/32][Cin_p][32] -- flip: a symmetric (same coordinates, odd kernel) map transposes by mirroring its offsets
-__global__ __launch_bounds__(256) void prep_weights_bf16_t_kernel(const float* __restrict__ w, __bf16* __restrict__ wt, int K,
-                                                                  int Cin, int Cout, int flip) {
-  const int Cp = conv_cout_padded(Cin);
-  const int64_t total = (int64_t)K * Cout * Cp;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    int cin, co, k;
-    weight_image_coords(t, Cout, Cp, &k, &co, &cin);              // co: a channel of grad_in (W's Cin), cin: of grad_out
-    const int ks = flip ? K - 1 - k : k;
-    wt[t] = (__bf16)(co < Cin ? w[((int64_t)ks * Cin + co) * Cout + cin] : 0.0f);
-  }
 }
 
 // prefetch registers of the A operand + their staging code, one specialisation per input format (keeps the unused
@@ -1830,34 +1748,6 @@ struct GoArgs {
   unsigned* counters;        // ... or, when given, by the last block of each tile: one zeroed word per (row tile, column tile)
 };
 
-// W fp32 [K][Cin][Cout] -> fp16 fragment-order image [2 planes interleaved below][...]: element order
-//   [k][slice][column tile of 32][plane][k-step (2)][lane (64)][8]   with lane = 32 * (kk / 8 % 2) + column % 32,
-//   kk = channel inside the slice = 16 * k-step + 8 * (lane / 32) + j  -- exactly the B operand registers of
-//   v_mfma_f32_32x32x16_f16, so that a wave fetches one fragment with one contiguous 1-KB load.  Trailer: max|W|.
-__global__ __launch_bounds__(256) void prep_weights_f16_frag_kernel(const float* __restrict__ w, uint16_t* __restrict__ wt, int K,
-                                                                    int Cin, int Cout, const float* __restrict__ amax) {
-  const int Cp = conv_cout_padded(Cout);
-  const int64_t total = (int64_t)K * Cin * Cp;              // elements per plane
-  const float am = read_amax(amax);
-  const float sc = f16_scale_for(am);
-  if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(wt + 2 * total) = am;
-  const int ns = Cin / BK, nt = Cp / 32;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    // t enumerates [k][slice][tile][ks][lane][j] (one plane); the two planes of a (k, slice, tile) are adjacent
-    const int j = (int)(t & 7), lane = (int)((t >> 3) & 63), ks = (int)((t >> 9) & 1);
-    int64_t q = t >> 10;
-    const int tile = (int)(q % nt); q /= nt;
-    const int slice = (int)(q % ns);
-    const int k = (int)(q / ns);
-    const int cin = slice * BK + ks * 16 + (lane >> 5) * 8 + j, co = tile * 32 + (lane & 31);
-    uint16_t hh, mm;
-    split2_f16(co < Cout ? w[((int64_t)k * Cin + cin) * Cout + co] * sc : 0.0f, hh, mm);
-    const int64_t base = (((int64_t)k * ns + slice) * nt + tile) * 2048 + ks * 512 + lane * 8 + j;    // 2 planes x 1024 per tile
-    wt[base] = hh;
-    wt[base + 1024] = mm;
-  }
-}
-
 #ifdef CNRMA_EXPERIMENTS
 #include "sparse_exp_go1.inc"
 #endif
@@ -2347,24 +2237,6 @@ constexpr int GOF_LDS = GOF_IMG * 4 + GO_BM * 27 * 2 + GO_UMAX * 4;
 static_assert(GOF_LDS <= 48 * 1024 && 4 * GOF_LDS <= 160 * 1024, "four blocks per CU");
 __device__ __forceinline__ int gof_slot(int row, int chunk) { return row * GOF_ROW + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
-// W fp32 [K][Cin][Cout] -> fragment-order image, element order [k][slice][column tile of 32][i (4)][lane (64)][e (4)]:
-// channel slice * 32 + 8 i + 4 (lane / 32) + e, column tile * 32 + lane % 32; columns padded to Cout_p with zeros
-__global__ __launch_bounds__(256) void prep_weights_f32_frag_kernel(const float* __restrict__ w, float* __restrict__ wt, int K,
-                                                                    int Cin, int Cout) {
-  const int Cp = conv_cout_padded(Cout);
-  const int64_t total = (int64_t)K * Cin * Cp;
-  const int ns = Cin / BK, nt = Cp / 32;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int e = (int)(t & 3), lane = (int)((t >> 2) & 63), i = (int)((t >> 8) & 3);
-    int64_t q = t >> 10;
-    const int tile = (int)(q % nt); q /= nt;
-    const int slice = (int)(q % ns);
-    const int k = (int)(q / ns);
-    const int cin = slice * BK + 8 * i + 4 * (lane >> 5) + e, co = tile * 32 + (lane & 31);
-    wt[t] = co < Cout ? w[((int64_t)k * Cin + cin) * Cout + co] : 0.0f;
-  }
-}
-
 
 template <int WAVES_N, int KS, bool HAS_RES>
 __global__ __launch_bounds__(256, 4) void sparse_conv_gof_kernel(ConvArgs p, GoArgs g, const float* __restrict__ wfrag, Go2Map mp) {
@@ -2657,13 +2529,42 @@ __global__ __launch_bounds__(256) void maxpool_kernel(const float* __restrict__ 
   out[t] = any ? m : 0.0f;
 }
 
-// per-channel sum / sum of squares in fp64, deterministic two-stage (partials [nblk][2C])
-__global__ __launch_bounds__(256) void colstats_partial_kernel(const float* __restrict__ in, int64_t n_cap,
-                                                               const int32_t* __restrict__ n_dev,
-                                                               const int32_t* __restrict__ row0_dev, int C,
-                                                               double* __restrict__ part) {
+// ---- deterministic fp64 column sums: one two-stage skeleton (partials [nblk][2C], then one block per channel) -----------------
+// Term: the two fp64 addends of element i = r * C + c.  Statistics: (v, v * v)
+struct StatsTerm {
+  const float* __restrict__ in;
+  __device__ __forceinline__ void operator()(int64_t i, double& a, double& b) const {
+    const double v = (double)in[i];
+    a = v;
+    b = v * v;
+  }
+};
+
+// gradient dy where the saved output y is positive; below: times y + 1 (act 2, ELU: d/dx = y + 1) or 0 (ReLU)
+__device__ __forceinline__ void mask_grad(float& g, float yv, int act) {
+  if (!(yv > 0.0f)) g = act == 2 ? g * (yv + 1.0f) : 0.0f;
+}
+
+// BatchNorm backward: (g, g * x) of the gradient, MASKED when y is given:
+// s1[c] = sum_r dy[r][c], s2[c] = sum_r dy[r][c] * x[r][c]; then
+// dgamma = (s2 - mean * s1) / sigma, dbeta = s1, dx = gamma / sigma * (dy - s1 / n - xhat * dgamma / n)
+struct GradTerm {
+  const float* __restrict__ dy; const float* __restrict__ x; const float* __restrict__ y; int act;
+  __device__ __forceinline__ void operator()(int64_t i, double& a, double& b) const {
+    float gf = dy[i];
+    if (y != nullptr) mask_grad(gf, y[i], act);
+    const double g = (double)gf;
+    a = g;
+    b = g * (double)x[i];
+  }
+};
+
+template <typename Term>
+__global__ __launch_bounds__(256) void colsum_partial_kernel(Term term, int64_t n_cap, const int32_t* __restrict__ n_dev,
+                                                             const int32_t* __restrict__ row0_dev, int C,
+                                                             double* __restrict__ part) {
   const int64_t n = live_rows(n_cap, n_dev);
-  if (row0_dev != nullptr) in += (int64_t)__builtin_nontemporal_load(row0_dev) * C;     // a scene's row segment
+  const int64_t i0 = row0_dev != nullptr ? (int64_t)__builtin_nontemporal_load(row0_dev) * C : 0;     // a scene's row segment
   // thread -> channel c = tid % C (C <= 256), row group = tid / C
   const int c = threadIdx.x % C;
   const int groups = blockDim.x / C;
@@ -2671,9 +2572,10 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* __re
   double s = 0.0, q = 0.0;
   if (gi < groups) {
     for (int64_t r = (int64_t)blockIdx.x * groups + gi; r < n; r += (int64_t)gridDim.x * groups) {
-      double v = (double)in[r * C + c];
-      s += v;
-      q += v * v;
+      double a, b;
+      term(i0 + r * C + c, a, b);
+      s += a;
+      q += b;
     }
   }
   __shared__ double sm[2 * 256];
@@ -2688,10 +2590,9 @@ __global__ __launch_bounds__(256) void colstats_partial_kernel(const float* __re
   }
 }
 
-// one block per channel: 256 lanes add the per-block partials in a fixed order (deterministic)
-__global__ __launch_bounds__(256) void colstats_final_kernel(const double* __restrict__ part, int nblk, int C, int64_t n_cap,
-                                                             const int32_t* __restrict__ n_dev, double* __restrict__ stats) {
-  const int c = blockIdx.x;
+// second stage, one block of 256 per channel: the lanes add the per-block partials of channel c in a fixed order (deterministic);
+// every thread calls it, thread 0 receives the two sums
+__device__ __forceinline__ void colsum_channel(const double* __restrict__ part, int nblk, int C, int c, double& s_out, double& q_out) {
   __shared__ double ss[256], qq[256];
   double s = 0.0, q = 0.0;
   for (int b = threadIdx.x; b < nblk; b += 256) { s += part[(int64_t)b * 2 * C + c]; q += part[(int64_t)b * 2 * C + C + c]; }
@@ -2701,14 +2602,74 @@ __global__ __launch_bounds__(256) void colstats_final_kernel(const double* __res
     if ((int)threadIdx.x < d) { ss[threadIdx.x] += ss[threadIdx.x + d]; qq[threadIdx.x] += qq[threadIdx.x + d]; }
     __syncthreads();
   }
+  if (threadIdx.x == 0) { s_out = ss[0]; q_out = qq[0]; }
+}
+
+// mean and biased variance of every channel; BatchNorm (running statistics given) also updates them here (running_var takes the
+// unbiased estimate, as nn.BatchNorm1d) and the batch counter -- eight tiny torch launches otherwise
+__global__ __launch_bounds__(256) void colstats_final_kernel(const double* __restrict__ part, int nblk, int C, int64_t n_cap,
+                                                             const int32_t* __restrict__ n_dev, double* __restrict__ stats,
+                                                             float momentum, float* __restrict__ running_mean,
+                                                             float* __restrict__ running_var, int64_t* __restrict__ batches) {
+  const int c = blockIdx.x;
+  double s = 0.0, q = 0.0;
+  colsum_channel(part, nblk, C, c, s, q);
   if (threadIdx.x == 0) {
-    const double n = (double)live_rows(n_cap, n_dev);
-    const double mean = ss[0] / n;
-    double var = qq[0] / n - mean * mean;   // biased variance
+    const double nn = (double)live_rows(n_cap, n_dev);
+    const double mean = s / nn;
+    double var = q / nn - mean * mean;   // biased variance
     if (var < 0.0) var = 0.0;
     stats[c] = mean;
     stats[C + c] = var;
+    if (running_mean != nullptr) running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
+    if (running_var != nullptr) running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)(var * (nn / (nn - 1.0)));
+    if (batches != nullptr && c == 0) *batches += 1;
   }
+}
+
+__global__ __launch_bounds__(256) void bn_backward_final_kernel(const double* __restrict__ part, int nblk, int C, int64_t n,
+                                                                const double* __restrict__ stats, float eps,
+                                                                float* __restrict__ dweight, float* __restrict__ dbias,
+                                                                double* __restrict__ sums) {
+  const int c = blockIdx.x;
+  double s = 0.0, q = 0.0;
+  colsum_channel(part, nblk, C, c, s, q);
+  if (threadIdx.x == 0) {
+    const double mean = stats[c], inv = 1.0 / sqrt(stats[C + c] + (double)eps);
+    const double dg = (q - mean * s) * inv;
+    if (dweight) dweight[c] = (float)dg;
+    if (dbias) dbias[c] = (float)s;
+    sums[c] = s / (double)n;              // mean(dy)
+    sums[C + c] = dg / (double)n;         // mean(dy * xhat)
+  }
+}
+
+// ---- normalise and apply: one channel's coefficients, the forward value, the backward value ---------------------------------
+// mean and 1 / sigma of channel c in fp32 from the fp64 statistics {mean[C], biased var[C]}.  The second half is indexed from its
+// own base (stats + C)[c], not stats[C + c]: called with c + j, the four channels of a lane then share one address register pair
+struct NormCoef { float mean, inv; };
+
+__device__ __forceinline__ NormCoef norm_coef(const double* stats, int C, int c, float eps) {
+  const double* var = stats + C;
+  return {(float)stats[c], 1.0f / sqrtf((float)var[c] + eps)};
+}
+
+// an absent gain / shift is skipped, not applied as 1 / 0: -0.0f + 0.0f is +0.0f
+__device__ __forceinline__ float norm_forward(float x, NormCoef k, const float* weight,
+                                              const float* bias, int c) {
+  float v = (x - k.mean) * k.inv;
+  if (weight) v = v * weight[c];
+  if (bias) v = v + bias[c];
+  return v;
+}
+
+// dx of the (masked) gradient g; sums = {mean(dy)[C], mean(dy * xhat)[C]} as bn_backward_final_kernel left them
+__device__ __forceinline__ float norm_backward(float g, float x, NormCoef k, const float* weight,
+                                               const double* sums, int C, int c) {
+  const double* sums2 = sums + C;
+  const float xhat = (x - k.mean) * k.inv;
+  const float gain = weight ? weight[c] : 1.0f;
+  return gain * k.inv * (g - (float)sums[c] - xhat * (float)sums2[c]);
 }
 
 __global__ __launch_bounds__(256) void instnorm_apply_kernel(const float* __restrict__ in, int64_t n_cap,
@@ -2726,11 +2687,7 @@ __global__ __launch_bounds__(256) void instnorm_apply_kernel(const float* __rest
   }
   for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * C; t += (int64_t)gridDim.x * blockDim.x) {
     const int c = (int)(t % C);
-    const float mean = (float)stats[c];
-    const float inv = 1.0f / sqrtf((float)stats[C + c] + eps);
-    float v = (in[t] - mean) * inv;
-    if (weight) v = v * weight[c];
-    if (bias) v = v + bias[c];
+    const float v = norm_forward(in[t], norm_coef(stats, C, c, eps), weight, bias, c);
     out[t] = relu ? fmaxf(v, 0.0f) : v;
   }
 }
@@ -2752,14 +2709,9 @@ __global__ __launch_bounds__(256) void instnorm_maxpool_kernel(const float* __re
   if (t < n * c4) {
     const int64_t o = t / c4;
     const int c = (int)(t - o * c4) * 4;
-    float mean[4], inv[4], w[4], b[4];
+    NormCoef kc[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      mean[j] = (float)stats[c + j];
-      inv[j] = 1.0f / sqrtf((float)stats[C + c + j] + eps);
-      w[j] = weight ? weight[c + j] : 1.0f;
-      b[j] = bias ? bias[c + j] : 0.0f;
-    }
+    for (int j = 0; j < 4; ++j) kc[j] = norm_coef(stats, C, c + j, eps);
     float m[4] = {-__builtin_inff(), -__builtin_inff(), -__builtin_inff(), -__builtin_inff()};
     bool any = false;
     for (int k = 0; k < K; ++k) {
@@ -2769,9 +2721,7 @@ __global__ __launch_bounds__(256) void instnorm_maxpool_kernel(const float* __re
         const float x[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          float v = (x[j] - mean[j]) * inv[j];
-          if (weight) v = v * w[j];
-          if (bias) v = v + b[j];
+          float v = norm_forward(x[j], kc[j], weight, bias, c + j);
           if (relu) v = fmaxf(v, 0.0f);
           m[j] = fmaxf(m[j], v);
         }
@@ -2788,105 +2738,11 @@ __global__ __launch_bounds__(256) void instnorm_maxpool_kernel(const float* __re
   }
 }
 
-// ---- BatchNorm (training) backward over the rows of a [n][C] matrix -----------------------------------------------------
-// s1[c] = sum_r dy[r][c], s2[c] = sum_r dy[r][c] * x[r][c] in fp64, deterministic two-stage like colstats; then
-// dgamma = (s2 - mean * s1) / sigma, dbeta = s1, dx = gamma / sigma * (dy - s1 / n - xhat * dgamma / n)
-__global__ __launch_bounds__(256) void colsum2_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                              int64_t n, int C, double* __restrict__ part) {
-  const int c = threadIdx.x % C;
-  const int groups = blockDim.x / C;
-  const int gi = threadIdx.x / C;
-  double s = 0.0, q = 0.0;
-  if (gi < groups) {
-    for (int64_t r = (int64_t)blockIdx.x * groups + gi; r < n; r += (int64_t)gridDim.x * groups) {
-      const double g = (double)dy[r * C + c];
-      s += g;
-      q += g * (double)x[r * C + c];
-    }
-  }
-  __shared__ double sm[2 * 256];
-  sm[threadIdx.x] = s;
-  sm[256 + threadIdx.x] = q;
-  __syncthreads();
-  if (threadIdx.x < C) {
-    double ts = 0.0, tq = 0.0;
-    for (int g = 0; g < groups; ++g) { ts += sm[g * C + threadIdx.x]; tq += sm[256 + g * C + threadIdx.x]; }
-    part[(int64_t)blockIdx.x * 2 * C + threadIdx.x] = ts;
-    part[(int64_t)blockIdx.x * 2 * C + C + threadIdx.x] = tq;
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_backward_final_kernel(const double* __restrict__ part, int nblk, int C, int64_t n,
-                                                                const double* __restrict__ stats, float eps,
-                                                                float* __restrict__ dweight, float* __restrict__ dbias,
-                                                                double* __restrict__ sums) {
-  const int c = blockIdx.x;
-  __shared__ double ss[256], qq[256];
-  double s = 0.0, q = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) { s += part[(int64_t)b * 2 * C + c]; q += part[(int64_t)b * 2 * C + C + c]; }
-  ss[threadIdx.x] = s; qq[threadIdx.x] = q;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { ss[threadIdx.x] += ss[threadIdx.x + d]; qq[threadIdx.x] += qq[threadIdx.x + d]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double mean = stats[c], inv = 1.0 / sqrt(stats[C + c] + (double)eps);
-    const double dg = (qq[0] - mean * ss[0]) * inv;
-    if (dweight) dweight[c] = (float)dg;
-    if (dbias) dbias[c] = (float)ss[0];
-    sums[c] = ss[0] / (double)n;          // mean(dy)
-    sums[C + c] = dg / (double)n;         // mean(dy * xhat)
-  }
-}
-
-__global__ __launch_bounds__(256) void bn_backward_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                int64_t n, int C, const double* __restrict__ stats,
-                                                                const double* __restrict__ sums,
-                                                                const float* __restrict__ weight, float eps,
-                                                                float* __restrict__ dx) {
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * C; t += (int64_t)gridDim.x * blockDim.x) {
-    const int c = (int)(t % C);
-    const float mean = (float)stats[c];
-    const float inv = 1.0f / sqrtf((float)stats[C + c] + eps);
-    const float xhat = (x[t] - mean) * inv;
-    const float g = weight ? weight[c] : 1.0f;
-    dx[t] = g * inv * (dy[t] - (float)sums[c] - xhat * (float)sums[C + c]);
-  }
-}
-
-// ---- BatchNorm (training) fused with what follows it in a residual block (round 5): y = [relu]( bn(x) [+ residual] ) ---------------
-// forward: column statistics as above (fp64 sums in a fixed order); the final stage also updates the running statistics
-// (running_var takes the unbiased estimate, as nn.BatchNorm1d) and the batch counter -- eight tiny torch launches otherwise;
+// ---- BatchNorm (training) over the rows of a [n][C] matrix, fused with what follows it in a residual block (round 5):
+// y = [relu]( bn(x) [+ residual] ) ------------------------------------------------------------------------------------------
+// forward: column statistics as above (fp64 sums in a fixed order, running statistics updated by colstats_final_kernel);
 // backward: with a ReLU behind the normalisation the incoming gradient is masked by y > 0 on the fly (y = the saved output),
 // the masked gradient is also the residual branch's gradient.
-__global__ __launch_bounds__(256) void bn_stats_final_kernel(const double* __restrict__ part, int nblk, int C, int64_t n,
-                                                             double* __restrict__ stats, float momentum,
-                                                             float* __restrict__ running_mean, float* __restrict__ running_var,
-                                                             int64_t* __restrict__ batches) {
-  const int c = blockIdx.x;
-  __shared__ double ss[256], qq[256];
-  double s = 0.0, q = 0.0;
-  for (int b = threadIdx.x; b < nblk; b += 256) { s += part[(int64_t)b * 2 * C + c]; q += part[(int64_t)b * 2 * C + C + c]; }
-  ss[threadIdx.x] = s; qq[threadIdx.x] = q;
-  __syncthreads();
-  for (int d = 128; d > 0; d >>= 1) {
-    if ((int)threadIdx.x < d) { ss[threadIdx.x] += ss[threadIdx.x + d]; qq[threadIdx.x] += qq[threadIdx.x + d]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    const double nn = (double)n;
-    const double mean = ss[0] / nn;
-    double var = qq[0] / nn - mean * mean;   // biased variance
-    if (var < 0.0) var = 0.0;
-    stats[c] = mean;
-    stats[C + c] = var;
-    if (running_mean != nullptr) running_mean[c] = (1.0f - momentum) * running_mean[c] + momentum * (float)mean;
-    if (running_var != nullptr) running_var[c] = (1.0f - momentum) * running_var[c] + momentum * (float)(var * (nn / (nn - 1.0)));
-    if (batches != nullptr && c == 0) *batches += 1;
-  }
-}
-
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ in, int64_t n, int C, const double* __restrict__ stats,
                                                        const float* __restrict__ weight, const float* __restrict__ bias, float eps,
                                                        const float* __restrict__ residual, int relu, float* __restrict__ out) {
@@ -2900,11 +2756,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     float o[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float mean = (float)stats[c + j];
-      const float inv = 1.0f / sqrtf((float)stats[C + c + j] + eps);
-      float v = (xv[j] - mean) * inv;
-      if (weight) v = v * weight[c + j];
-      if (bias) v = v + bias[c + j];
+      float v = norm_forward(xv[j], norm_coef(stats, C, c + j, eps), weight, bias, c + j);
       if (residual) v = v + rv[j];
       o[j] = relu == 1 ? fmaxf(v, 0.0f) : (relu == 2 ? (v > 0.0f ? v : expm1f(v)) : v);      // 2: ELU (alpha 1)
     }
@@ -2912,35 +2764,15 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
   }
 }
 
-// s1 / s2 of the MASKED gradient (y given: dy counts where y > 0)
-__global__ __launch_bounds__(256) void bn_colsum2_partial_kernel(const float* __restrict__ dy, const float* __restrict__ x,
-                                                                 const float* __restrict__ y, int act, int64_t n, int C,
-                                                                 double* __restrict__ part) {
-  const int c = threadIdx.x % C;
-  const int groups = blockDim.x / C;
-  const int gi = threadIdx.x / C;
-  double s = 0.0, q = 0.0;
-  if (gi < groups) {
-    for (int64_t r = (int64_t)blockIdx.x * groups + gi; r < n; r += (int64_t)gridDim.x * groups) {
-      float gf = dy[r * C + c];
-      if (y != nullptr) {
-        const float yv = y[r * C + c];
-        if (!(yv > 0.0f)) gf = act == 2 ? gf * (yv + 1.0f) : 0.0f;        // ELU: d/dx = y + 1 below zero; ReLU: 0
-      }
-      const double g = (double)gf;
-      s += g;
-      q += g * (double)x[r * C + c];
-    }
-  }
-  __shared__ double sm[2 * 256];
-  sm[threadIdx.x] = s;
-  sm[256 + threadIdx.x] = q;
-  __syncthreads();
-  if (threadIdx.x < C) {
-    double ts = 0.0, tq = 0.0;
-    for (int g = 0; g < groups; ++g) { ts += sm[g * C + threadIdx.x]; tq += sm[256 + g * C + threadIdx.x]; }
-    part[(int64_t)blockIdx.x * 2 * C + threadIdx.x] = ts;
-    part[(int64_t)blockIdx.x * 2 * C + C + threadIdx.x] = tq;
+// the scalar backward for any C (cnrma_bn_backward_f32: no activation, no residual)
+__global__ __launch_bounds__(256) void bn_backward_apply_kernel(const float* __restrict__ dy, const float* __restrict__ x,
+                                                                int64_t n, int C, const double* __restrict__ stats,
+                                                                const double* __restrict__ sums,
+                                                                const float* __restrict__ weight, float eps,
+                                                                float* __restrict__ dx) {
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n * C; t += (int64_t)gridDim.x * blockDim.x) {
+    const int c = (int)(t % C);
+    dx[t] = norm_backward(dy[t], x[t], norm_coef(stats, C, c, eps), weight, sums, C, c);
   }
 }
 
@@ -2959,17 +2791,12 @@ __global__ __launch_bounds__(256) void bn_backward_apply2_kernel(const float* __
       const float4 y4 = reinterpret_cast<const float4*>(y)[t];
       const float yv[4] = {y4.x, y4.y, y4.z, y4.w};
 #pragma unroll
-      for (int j = 0; j < 4; ++j) if (!(yv[j] > 0.0f)) gv[j] = act == 2 ? gv[j] * (yv[j] + 1.0f) : 0.0f;
+      for (int j = 0; j < 4; ++j) mask_grad(gv[j], yv[j], act);
     }
     float o[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float mean = (float)stats[c + j];
-      const float inv = 1.0f / sqrtf((float)stats[C + c + j] + eps);
-      const float xhat = (xv[j] - mean) * inv;
-      const float g = weight ? weight[c + j] : 1.0f;
-      o[j] = g * inv * (gv[j] - (float)sums[c + j] - xhat * (float)sums[C + c + j]);
-    }
+    for (int j = 0; j < 4; ++j)
+      o[j] = norm_backward(gv[j], xv[j], norm_coef(stats, C, c + j, eps), weight, sums, C, c + j);
     reinterpret_cast<float4*>(dx)[t] = make_float4(o[0], o[1], o[2], o[3]);
     if (dres != nullptr) reinterpret_cast<float4*>(dres)[t] = make_float4(gv[0], gv[1], gv[2], gv[3]);
   }
@@ -3900,17 +3727,6 @@ extern "C" int cnrma_sparse_conv_f32(const float* in_feats, int Cin, const int32
   return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_EXACT, nullptr, workspace_bytes, as_stream(stream));
 }
 
-extern "C" int cnrma_sparse_conv_prepare_weights(const float* weight, int K, int Cin, int Cout, void* weight_split,
-                                                 void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0) return CNRMA_EINVAL;
-  int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  int64_t blocks = capped_blocks(total, 4096);
-  hipLaunchKernelGGL(prep_weights_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<__bf16*>(weight_split), K, Cin, Cout);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
 extern "C" int cnrma_sparse_conv_bf16x6(const float* in_feats, const void* in_split, int64_t in_zero_row, int Cin,
                                         const int32_t* nbr, int K, const void* weight_split, int Cout,
                                         const float* scale, const float* shift, const float* residual, int act,
@@ -3987,34 +3803,259 @@ extern "C" int cnrma_absmax_f32(const float* in, int64_t n_cap, const int32_t* n
   return 0;
 }
 
-extern "C" size_t cnrma_sparse_conv_weight_bytes(int K, int Cin, int Cout) {
-  return (size_t)3 * K * Cin * conv_cout_padded(Cout) * sizeof(uint16_t);
-}
-
 extern "C" size_t cnrma_amax_bytes(void) { return sizeof(float) * AMAX_SLOTS * AMAX_STRIDE; }
 
-extern "C" size_t cnrma_sparse_conv_f16_weight_bytes(int K, int Cin, int Cout) {
-  return (size_t)2 * K * Cin * conv_cout_padded(Cout) * sizeof(uint16_t) + 64 + sizeof(float) * AMAX_SLOTS * AMAX_STRIDE;
+// ================================================================================================================
+// Prepared weight images.  Every image is the same loop over its elements t, made of three parts:
+//   ORDER   where element t comes from -- (offset k, input channel cin, output column co) of the image's [K][Ci][Co] weights, the
+//           columns padded to Cout_p = conv_cout_padded(Co) with zeros -- and where its planes go;
+//   SOURCE  which W element that is: W itself, or the data gradient's weights W'[k] = W[flip ? K - 1 - k : k]^T ([Cout] -> [Cin];
+//           flip: a symmetric (same coordinates, odd kernel) map transposes by mirroring its offsets);
+//   ENCODER how the value is written: fp32, bf16 (round to nearest), bf16 hi / mid / lo (exact split by truncation), or fp16 hi / lo
+//           scaled by f16_scale_for(max|W|), the bound stored in a trailer word behind the planes.
+// oracle/sparse_oracle.py weight_image() states the same layouts on the host; tests/test_weight_images_gpu.py compares bytes.
+// ================================================================================================================
+namespace {
+
+// stage order, per plane [K][Ci / 32][Cout_p][32] -- the 32-channel slice of ALL columns of one offset is contiguous (Ci % 32 == 0:
+// the only case the MFMA kernels take; other channel counts keep the plain [K][Cout_p][Ci] order and are never read).  Plane p
+// follows plane p - 1.  (Every order's offset() takes (t, plane, planes, elements per plane) and uses what its layout needs.)
+struct StageOrder {
+  __device__ static void coords(int64_t t, int Ci, int Cp, int* k, int* cin, int* co) {
+    if ((Ci & (BK - 1)) == 0) {
+      const int c32 = (int)(t & (BK - 1));
+      const int64_t q = t / BK;
+      *co = (int)(q % Cp);
+      const int64_t q2 = q / Cp;
+      const int ns = Ci / BK;
+      *cin = (int)(q2 % ns) * BK + c32;
+      *k = (int)(q2 / ns);
+    } else {
+      *cin = (int)(t % Ci);
+      const int64_t q = t / Ci;
+      *co = (int)(q % Cp);
+      *k = (int)(q / Cp);
+    }
+  }
+  __device__ static int64_t offset(int64_t t, int plane, int planes, int64_t total) { return t + plane * total; }
+};
+
+// the fragment orders are [k][slice of 32 channels][column tile of 32][1024 elements of the tile]: t >> 10 -> (k, slice, tile)
+__device__ __forceinline__ void frag_tile_coords(int64_t t, int Ci, int Cp, int* k, int* slice, int* tile) {
+  const int ns = Ci / BK, nt = Cp / 32;
+  int64_t q = t >> 10;
+  *tile = (int)(q % nt); q /= nt;
+  *slice = (int)(q % ns);
+  *k = (int)(q / ns);
 }
 
-extern "C" int cnrma_sparse_conv_prepare_weights_f16(const float* weight, int K, int Cin, int Cout, void* weight_split,
-                                                     void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0 || weight_split == nullptr) return CNRMA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  const int64_t total_src = (int64_t)K * Cin * Cout;
-  const int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  uint16_t* wt = reinterpret_cast<uint16_t*>(weight_split);
-  float* amax = reinterpret_cast<float*>(wt + 2 * total) + 16;       // slot scratch behind the 64-byte trailer
-  hipError_t e = cnrma_fill_bytes(amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
-  if (e != hipSuccess) return -(int)e;
-  int64_t blocks = capped_blocks(total_src / 4 + 1, 2048);
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, total_src, nullptr, 1, amax);
-  blocks = capped_blocks(total, 4096);
-  hipLaunchKernelGGL(prep_weights_f16_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, wt, K, Cin, Cout, amax);
+// 16-bit MFMA fragment order: inside a tile [k-step (2)][lane (64)][8] with lane = 32 * (kk / 8 % 2) + column % 32,
+// kk = channel inside the slice = 16 * k-step + 8 * (lane / 32) + j -- exactly the B operand registers of
+// v_mfma_f32_32x32x16_{f16,bf16}, so that a wave fetches one fragment with one contiguous 1-KB load.  Two planes (fp16 hi / lo)
+// are interleaved per tile: [k][slice][tile][plane][k-step][lane][8]
+struct Frag16Order {
+  __device__ static void coords(int64_t t, int Ci, int Cp, int* k, int* cin, int* co) {
+    const int j = (int)(t & 7), lane = (int)((t >> 3) & 63), ks = (int)((t >> 9) & 1);
+    int slice, tile;
+    frag_tile_coords(t, Ci, Cp, k, &slice, &tile);
+    *cin = slice * BK + ks * 16 + (lane >> 5) * 8 + j;
+    *co = tile * 32 + (lane & 31);
+  }
+  __device__ static int64_t offset(int64_t t, int plane, int planes, int64_t total) {
+    return (t >> 10) * (1024 * planes) + plane * 1024 + (t & 1023);
+  }
+};
+
+// fp32 fragment order: inside a tile [i (4)][lane (64)][e (4)]: channel slice * 32 + 8 i + 4 (lane / 32) + e, column
+// tile * 32 + lane % 32 (one 16-byte load per lane and read of sparse_conv_gof_kernel)
+struct Frag32Order {
+  __device__ static void coords(int64_t t, int Ci, int Cp, int* k, int* cin, int* co) {
+    const int e = (int)(t & 3), lane = (int)((t >> 2) & 63), i = (int)((t >> 8) & 3);
+    int slice, tile;
+    frag_tile_coords(t, Ci, Cp, k, &slice, &tile);
+    *cin = slice * BK + 8 * i + 4 * (lane >> 5) + e;
+    *co = tile * 32 + (lane & 31);
+  }
+  __device__ static int64_t offset(int64_t t, int plane, int planes, int64_t total) { return t; }
+};
+
+// element (k, cin, co) of the image's weights, read from W fp32 [K][Cin][Cout]; co < the image's columns
+__device__ __forceinline__ float weight_source(const float* __restrict__ w, int K, int Cin, int Cout, int k, int cin, int co,
+                                               bool transpose, bool flip) {
+  if (!transpose) return w[((int64_t)k * Cin + cin) * Cout + co];
+  const int ks = flip ? K - 1 - k : k;
+  return w[((int64_t)ks * Cin + co) * Cout + cin];          // co: a channel of grad_in (W's Cin), cin: of grad_out
+}
+
+struct EncodeF32 {
+  typedef float T;
+  static constexpr int PLANES = 1;
+  static constexpr bool SCALED = false;
+  __device__ static void encode(float v, float, T* e) { e[0] = v; }
+};
+struct EncodeBf16 {                                           // round to nearest
+  typedef __bf16 T;
+  static constexpr int PLANES = 1;
+  static constexpr bool SCALED = false;
+  __device__ static void encode(float v, float, T* e) { e[0] = (__bf16)v; }
+};
+struct EncodeBf16x3 {                                         // v == hi + mid + lo exactly
+  typedef uint16_t T;
+  static constexpr int PLANES = 3;
+  static constexpr bool SCALED = false;
+  __device__ static void encode(float v, float, T* e) { split3_trunc(v, e[0], e[1], e[2]); }
+};
+struct EncodeF16x2 {                                          // v * scale ~ hi + lo, scale = f16_scale_for(max|W|) (a power of two)
+  typedef uint16_t T;
+  static constexpr int PLANES = 2;
+  static constexpr bool SCALED = true;
+  __device__ static void encode(float v, float scale, T* e) { split2_f16(v * scale, e[0], e[1]); }
+};
+
+__host__ __device__ inline int64_t weight_image_elems(int K, int Ci, int Co) { return (int64_t)K * Ci * conv_cout_padded(Co); }
+
+// element t of one image (all its planes)
+template <class Order, class Enc>
+__device__ __forceinline__ void weight_image_element(const float* __restrict__ w, int K, int Cin, int Cout, bool transpose, bool flip,
+                                                     float scale, typename Enc::T* __restrict__ img, int64_t t) {
+  const int Ci = transpose ? Cout : Cin, Co = transpose ? Cin : Cout;       // the image's input / output channels
+  const int Cp = conv_cout_padded(Co);
+  int k, cin, co;
+  Order::coords(t, Ci, Cp, &k, &cin, &co);
+  typename Enc::T e[Enc::PLANES];
+  Enc::encode(co < Co ? weight_source(w, K, Cin, Cout, k, cin, co, transpose, flip) : 0.0f, scale, e);
+#pragma unroll
+  for (int p = 0; p < Enc::PLANES; ++p) img[Order::offset(t, p, Enc::PLANES, (int64_t)K * Ci * Cp)] = e[p];
+}
+
+// one image, or (PAIR) two in ONE launch over the joined range: `img` as `transpose` says, then `img_t`, the transposed one
+// (training: the forward's and the mirrored-transposed one of its data gradient).  amax: the slots of max|W|.  img_t is read only
+// when PAIR, amax only when Enc::SCALED: every other instantiation is launched with nullptr there
+template <class Order, class Enc, bool PAIR>
+__global__ __launch_bounds__(256) void weight_image_kernel(const float* __restrict__ w, int K, int Cin, int Cout, int transpose,
+                                                           int flip, typename Enc::T* __restrict__ img,
+                                                           typename Enc::T* __restrict__ img_t, const float* __restrict__ amax) {
+  const int64_t total = transpose ? weight_image_elems(K, Cout, Cin) : weight_image_elems(K, Cin, Cout);
+  const int64_t total_t = PAIR ? weight_image_elems(K, Cout, Cin) : 0;
+  float scale = 1.0f;
+  if constexpr (Enc::SCALED) {
+    const float am = read_amax(amax);
+    scale = f16_scale_for(am);
+    if (blockIdx.x == 0 && threadIdx.x == 0) *reinterpret_cast<float*>(img + Enc::PLANES * total) = am;      // the trailer
+  }
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total + total_t; t += (int64_t)gridDim.x * blockDim.x) {
+    if (PAIR && t >= total) weight_image_element<Order, Enc>(w, K, Cin, Cout, true, flip != 0, scale, img_t, t - total);
+    else weight_image_element<Order, Enc>(w, K, Cin, Cout, transpose != 0, flip != 0, scale, img, t);
+  }
+}
+
+template <class Order, class Enc, bool PAIR = false>
+int launch_weight_image(const float* weight, int K, int Cin, int Cout, int transpose, int flip, void* image, void* image_t,
+                        const float* amax, hipStream_t st) {
+  typedef typename Enc::T T;
+  const int64_t total = (transpose ? weight_image_elems(K, Cout, Cin) : weight_image_elems(K, Cin, Cout)) +
+                        (PAIR ? weight_image_elems(K, Cout, Cin) : 0);
+  const int64_t blocks = capped_blocks(total, PAIR ? 8192 : 4096);
+  hipLaunchKernelGGL((weight_image_kernel<Order, Enc, PAIR>), dim3((unsigned)blocks), dim3(256), 0, st, weight, K, Cin, Cout,
+                     transpose ? 1 : 0, flip ? 1 : 0, reinterpret_cast<T*>(image), reinterpret_cast<T*>(image_t), amax);
   CNRMA_LAUNCH_CHECK();
   return 0;
 }
 
+// the fp16 images: max|W| first (into the slot scratch behind the 64-byte trailer), then the scaled image
+template <class Order>
+int prepare_weights_f16(const float* weight, int K, int Cin, int Cout, void* image, hipStream_t st) {
+  const int64_t total_src = (int64_t)K * Cin * Cout;
+  float* amax = reinterpret_cast<float*>(reinterpret_cast<uint16_t*>(image) + 2 * weight_image_elems(K, Cin, Cout)) + 16;
+  hipError_t e = cnrma_fill_bytes(amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
+  if (e != hipSuccess) return -(int)e;
+  const int64_t blocks = capped_blocks(total_src / 4 + 1, 2048);
+  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, total_src, nullptr, 1, amax);
+  return launch_weight_image<Order, EncodeF16x2>(weight, K, Cin, Cout, 0, 0, image, nullptr, amax, st);
+}
+
+}  // namespace
+
+extern "C" size_t cnrma_sparse_conv_weight_bytes(int K, int Cin, int Cout) {
+  return (size_t)3 * weight_image_elems(K, Cin, Cout) * sizeof(uint16_t);
+}
+
+extern "C" size_t cnrma_sparse_conv_f16_weight_bytes(int K, int Cin, int Cout) {
+  return (size_t)2 * weight_image_elems(K, Cin, Cout) * sizeof(uint16_t) + 64 + sizeof(float) * AMAX_SLOTS * AMAX_STRIDE;
+}
+
+extern "C" size_t cnrma_sparse_conv_bf16_weight_bytes(int K, int Cin, int Cout) {
+  return (size_t)weight_image_elems(K, Cin, Cout) * sizeof(uint16_t);
+}
+
+extern "C" size_t cnrma_sparse_conv_f32_frag_weight_bytes(int K, int Cin, int Cout) {
+  return (size_t)weight_image_elems(K, Cin, Cout) * sizeof(float);
+}
+
+extern "C" size_t cnrma_sparse_conv_bf16_frag_weight_bytes(int K, int Cin, int Cout) {
+  return (size_t)weight_image_elems(K, Cin, Cout) * 2;
+}
+
+// W fp32 [K][Cin][Cout] -> bf16 [3 planes][K][Cin/32][Cout_p][32]
+extern "C" int cnrma_sparse_conv_prepare_weights(const float* weight, int K, int Cin, int Cout, void* weight_split,
+                                                 void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || weight == nullptr || weight_split == nullptr) return CNRMA_EINVAL;
+  return launch_weight_image<StageOrder, EncodeBf16x3>(weight, K, Cin, Cout, 0, 0, weight_split, nullptr, nullptr, as_stream(stream));
+}
+
+// -> fp16 [2 planes][K][Cin/32][Cout_p][32] scaled, + trailer float = max|W|
+extern "C" int cnrma_sparse_conv_prepare_weights_f16(const float* weight, int K, int Cin, int Cout, void* weight_split,
+                                                     void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || weight == nullptr || weight_split == nullptr) return CNRMA_EINVAL;
+  return prepare_weights_f16<StageOrder>(weight, K, Cin, Cout, weight_split, as_stream(stream));
+}
+
+// -> bf16 [K][Cin/32][Cout_p][32], round to nearest (MODE 2)
+extern "C" int cnrma_sparse_conv_prepare_weights_bf16(const float* weight, int K, int Cin, int Cout, void* weight_bf16,
+                                                      void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || weight == nullptr || weight_bf16 == nullptr) return CNRMA_EINVAL;
+  return launch_weight_image<StageOrder, EncodeBf16>(weight, K, Cin, Cout, 0, 0, weight_bf16, nullptr, nullptr, as_stream(stream));
+}
+
+// -> the same image of the TRANSPOSED weights for dgrad, straight from W: bf16 [K][Cout/32][Cin_p][32]
+extern "C" int cnrma_sparse_conv_prepare_weights_bf16_t(const float* weight, int K, int Cin, int Cout, int flip,
+                                                        void* weight_bf16, void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || Cout % 32 != 0 || weight == nullptr || weight_bf16 == nullptr) return CNRMA_EINVAL;
+  return launch_weight_image<StageOrder, EncodeBf16>(weight, K, Cin, Cout, 1, flip, weight_bf16, nullptr, nullptr, as_stream(stream));
+}
+
+// -> fp32 fragment-order image (the exact gather-once convolution)
+extern "C" int cnrma_sparse_conv_prepare_weights_f32_frag(const float* weight, int K, int Cin, int Cout, void* weight_frag,
+                                                          void* stream) {
+  if (weight == nullptr || weight_frag == nullptr || K <= 0 || Cin <= 0 || Cin % BK != 0 || Cout <= 0) return CNRMA_EINVAL;
+  return launch_weight_image<Frag32Order, EncodeF32>(weight, K, Cin, Cout, 0, 0, weight_frag, nullptr, nullptr, as_stream(stream));
+}
+
+// -> fp16 fragment-order image, two planes interleaved per tile, scaled, + trailer float = max|W|
+extern "C" int cnrma_sparse_conv_prepare_weights_f16_frag(const float* weight, int K, int Cin, int Cout, void* weight_frag,
+                                                          void* stream) {
+  if (K <= 0 || Cin <= 0 || Cin % BK != 0 || Cout <= 0 || weight == nullptr || weight_frag == nullptr) return CNRMA_EINVAL;
+  return prepare_weights_f16<Frag16Order>(weight, K, Cin, Cout, weight_frag, as_stream(stream));
+}
+
+// -> bf16 fragment-order image of W (transpose == 0) or of the data gradient's weights (transpose == 1)
+extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag(const float* weight, int K, int Cin, int Cout, int transpose, int flip,
+                                                           void* weight_frag, void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || (transpose ? Cout : Cin) % BK != 0 || weight == nullptr || weight_frag == nullptr)
+    return CNRMA_EINVAL;
+  return launch_weight_image<Frag16Order, EncodeBf16>(weight, K, Cin, Cout, transpose, flip, weight_frag, nullptr, nullptr,
+                                                      as_stream(stream));
+}
+
+// -> both bf16 fragment-order images in one launch
+extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag_pair(const float* weight, int K, int Cin, int Cout, int flip,
+                                                                void* frag_forward, void* frag_transposed, void* stream) {
+  if (K <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BK != 0 || weight == nullptr || frag_forward == nullptr ||
+      frag_transposed == nullptr)
+    return CNRMA_EINVAL;
+  return launch_weight_image<Frag16Order, EncodeBf16, true>(weight, K, Cin, Cout, 0, flip, frag_forward, frag_transposed, nullptr,
+                                                            as_stream(stream));
+}
 
 // ---- pair-list convolution: layers whose kernel map is nearly empty -----------------------------------------------------
 // The output-stationary kernel multiplies a whole 64/128-row tile by W[k] as soon as ONE row of the tile has a neighbour
@@ -4400,22 +4441,7 @@ static GoArgs go_args(const void* tile_union, int64_t no_cap) {
   return g;
 }
 
-// ---- exact-fp32 gather-once convolution: weight image, launcher -------------------------------------------------------------
-extern "C" size_t cnrma_sparse_conv_f32_frag_weight_bytes(int K, int Cin, int Cout) {
-  return (size_t)K * Cin * conv_cout_padded(Cout) * sizeof(float);
-}
-
-extern "C" int cnrma_sparse_conv_prepare_weights_f32_frag(const float* weight, int K, int Cin, int Cout, void* weight_frag,
-                                                          void* stream) {
-  if (weight == nullptr || weight_frag == nullptr || K <= 0 || Cin <= 0 || Cin % BK != 0 || Cout <= 0) return CNRMA_EINVAL;
-  const int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  int64_t blocks = capped_blocks(total, 4096);
-  hipLaunchKernelGGL(prep_weights_f32_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<float*>(weight_frag), K, Cin, Cout);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
+// ---- exact-fp32 gather-once convolution: launcher ----------------------------------------------------------------------------
 extern "C" int cnrma_sparse_conv_go_f32(const float* in_feats, int Cin, const void* tile_union, const void* weight_frag, int Cout,
                                         const float* scale, const float* shift, const float* residual, int act, float* out_feats,
                                         int64_t no_cap, const int32_t* no_dev, void* workspace, size_t workspace_bytes, void* stream) {
@@ -4483,98 +4509,6 @@ extern "C" int cnrma_sparse_conv_wgrad_go_bf16(const float* in_feats, int Cin, c
   return 0;
 }
 
-extern "C" int cnrma_sparse_conv_prepare_weights_f16_frag(const float* weight, int K, int Cin, int Cout, void* weight_frag,
-                                                          void* stream) {
-  if (K <= 0 || Cin <= 0 || Cin % BK != 0 || Cout <= 0 || weight_frag == nullptr) return CNRMA_EINVAL;
-  hipStream_t st = as_stream(stream);
-  const int64_t total_src = (int64_t)K * Cin * Cout;
-  const int64_t total = (int64_t)K * Cin * conv_cout_padded(Cout);
-  uint16_t* wt = reinterpret_cast<uint16_t*>(weight_frag);
-  float* amax = reinterpret_cast<float*>(wt + 2 * total) + 16;       // slot scratch behind the 64-byte trailer
-  hipError_t e = cnrma_fill_bytes(amax, 0, sizeof(float) * AMAX_SLOTS * AMAX_STRIDE, st);
-  if (e != hipSuccess) return -(int)e;
-  int64_t blocks = capped_blocks(total_src / 4 + 1, 2048);
-  hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, total_src, nullptr, 1, amax);
-  blocks = capped_blocks(total, 4096);
-  hipLaunchKernelGGL(prep_weights_f16_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, st, weight, wt, K, Cin, Cout, amax);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
-// W fp32 [K][Cin][Cout] -> bf16 fragment-order image [k][slice][column tile of 32][k-step (2)][lane (64)][8] of
-//   transpose == 0:  W itself;   transpose == 1: the data gradient's weights W'[k] = W[flip ? K - 1 - k : k]^T ([Cout] -> [Cin])
-// (lane = 32 * (kk / 8 % 2) + column % 32, kk = channel inside the slice = 16 * k-step + 8 * (lane / 32) + j: the B operand
-// registers of v_mfma_f32_32x32x16_bf16 -- one contiguous 1-KB load per wave and k-step)
-__global__ __launch_bounds__(256) void prep_weights_bf16_frag_kernel(const float* __restrict__ w, __bf16* __restrict__ wt, int K,
-                                                                     int Cin, int Cout, int transpose, int flip) {
-  const int Ci = transpose ? Cout : Cin, Co = transpose ? Cin : Cout;       // the image's input / output channels
-  const int Cp = conv_cout_padded(Co);
-  const int64_t total = (int64_t)K * Ci * Cp;
-  const int ns = Ci / BK, nt = Cp / 32;
-  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (int64_t)gridDim.x * blockDim.x) {
-    const int j = (int)(t & 7), lane = (int)((t >> 3) & 63), ks = (int)((t >> 9) & 1);
-    int64_t q = t >> 10;
-    const int tile = (int)(q % nt); q /= nt;
-    const int slice = (int)(q % ns);
-    const int k = (int)(q / ns);
-    const int cin = slice * BK + ks * 16 + (lane >> 5) * 8 + j, co = tile * 32 + (lane & 31);
-    const int ksrc = transpose && flip ? K - 1 - k : k;
-    float v = 0.0f;
-    if (co < Co) v = transpose ? w[((int64_t)ksrc * Cin + co) * Cout + cin] : w[((int64_t)ksrc * Cin + cin) * Cout + co];
-    wt[t] = (__bf16)v;
-  }
-}
-
-// both images of a weight tensor in ONE launch (training: the forward's and the mirrored-transposed one of its data gradient)
-__global__ __launch_bounds__(256) void prep_weights_bf16_frag_pair_kernel(const float* __restrict__ w, __bf16* __restrict__ wf,
-                                                                          __bf16* __restrict__ wtr, int K, int Cin, int Cout, int flip) {
-  const int64_t total_f = (int64_t)K * Cin * conv_cout_padded(Cout), total_t = (int64_t)K * Cout * conv_cout_padded(Cin);
-  for (int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t0 < total_f + total_t; t0 += (int64_t)gridDim.x * blockDim.x) {
-    const bool tr = t0 >= total_f;
-    const int64_t t = tr ? t0 - total_f : t0;
-    const int Ci = tr ? Cout : Cin, Co = tr ? Cin : Cout;
-    const int ns = Ci / BK, nt = conv_cout_padded(Co) / 32;
-    const int j = (int)(t & 7), lane = (int)((t >> 3) & 63), ks = (int)((t >> 9) & 1);
-    int64_t q = t >> 10;
-    const int tile = (int)(q % nt); q /= nt;
-    const int slice = (int)(q % ns);
-    const int k = (int)(q / ns);
-    const int cin = slice * BK + ks * 16 + (lane >> 5) * 8 + j, co = tile * 32 + (lane & 31);
-    const int ksrc = tr && flip ? K - 1 - k : k;
-    float v = 0.0f;
-    if (co < Co) v = tr ? w[((int64_t)ksrc * Cin + co) * Cout + cin] : w[((int64_t)ksrc * Cin + cin) * Cout + co];
-    (tr ? wtr : wf)[t] = (__bf16)v;
-  }
-}
-
-extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag_pair(const float* weight, int K, int Cin, int Cout, int flip,
-                                                                void* frag_forward, void* frag_transposed, void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK != 0 || Cout % BK != 0 || weight == nullptr || frag_forward == nullptr ||
-      frag_transposed == nullptr)
-    return CNRMA_EINVAL;
-  int64_t blocks = capped_blocks((int64_t)K * Cin * conv_cout_padded(Cout) + (int64_t)K * Cout * conv_cout_padded(Cin), 8192);
-  hipLaunchKernelGGL(prep_weights_bf16_frag_pair_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<__bf16*>(frag_forward), reinterpret_cast<__bf16*>(frag_transposed), K, Cin, Cout, flip ? 1 : 0);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" size_t cnrma_sparse_conv_bf16_frag_weight_bytes(int K, int Cin, int Cout) {
-  return (size_t)K * Cin * conv_cout_padded(Cout) * 2;
-}
-
-extern "C" int cnrma_sparse_conv_prepare_weights_bf16_frag(const float* weight, int K, int Cin, int Cout, int transpose, int flip,
-                                                           void* weight_frag, void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0 || (transpose ? Cout : Cin) % BK != 0 || weight == nullptr || weight_frag == nullptr)
-    return CNRMA_EINVAL;
-  const int Ci = transpose ? Cout : Cin, Co = transpose ? Cin : Cout;
-  int64_t blocks = capped_blocks((int64_t)K * Ci * conv_cout_padded(Co), 4096);
-  hipLaunchKernelGGL(prep_weights_bf16_frag_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<__bf16*>(weight_frag), K, Cin, Cout, transpose ? 1 : 0, flip ? 1 : 0);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
 extern "C" int cnrma_sparse_conv_go_bf16(const float* in_feats, int Cin, const void* tile_union, const void* weight_frag, int Cout,
                                          float* out_feats, int64_t no_cap, const int32_t* no_dev, void* workspace,
                                          size_t workspace_bytes, void* stream) {
@@ -4620,30 +4554,6 @@ extern "C" int cnrma_sparse_conv_f16x3(const float* in_feats, const float* in_am
   ConvArgs p = conv_args(in_feats, Cin, nbr, K, Cout, out_feats, no_cap, no_dev, workspace);
   p.in_amax = in_amax; p.out_amax = out_amax;
   return launch_conv(with_epilogue(p, scale, shift, residual, act), CONV_F16X3, weight_split, workspace_bytes, as_stream(stream));
-}
-
-extern "C" size_t cnrma_sparse_conv_bf16_weight_bytes(int K, int Cin, int Cout) {
-  return (size_t)K * Cin * conv_cout_padded(Cout) * sizeof(uint16_t);
-}
-
-extern "C" int cnrma_sparse_conv_prepare_weights_bf16(const float* weight, int K, int Cin, int Cout, void* weight_bf16,
-                                                      void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0 || weight_bf16 == nullptr) return CNRMA_EINVAL;
-  int64_t blocks = capped_blocks((int64_t)K * Cin * conv_cout_padded(Cout), 4096);
-  hipLaunchKernelGGL(prep_weights_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<__bf16*>(weight_bf16), K, Cin, Cout);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
-}
-
-extern "C" int cnrma_sparse_conv_prepare_weights_bf16_t(const float* weight, int K, int Cin, int Cout, int flip,
-                                                        void* weight_bf16, void* stream) {
-  if (K <= 0 || Cin <= 0 || Cout <= 0 || Cout % 32 != 0 || weight == nullptr || weight_bf16 == nullptr) return CNRMA_EINVAL;
-  int64_t blocks = capped_blocks((int64_t)K * Cout * conv_cout_padded(Cin), 4096);
-  hipLaunchKernelGGL(prep_weights_bf16_t_kernel, dim3((unsigned)blocks), dim3(256), 0, as_stream(stream), weight,
-                     reinterpret_cast<__bf16*>(weight_bf16), K, Cin, Cout, flip ? 1 : 0);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
 }
 
 extern "C" int cnrma_sparse_conv_bf16(const float* in_feats, int Cin, const int32_t* nbr, int K, const void* weight_bf16,
@@ -4733,8 +4643,10 @@ extern "C" int cnrma_sparse_instnorm_f32(const float* in_feats, int64_t n_cap, c
   hipStream_t st = as_stream(stream);
   const int nblk = 1024;
   double* part = stats_ws + 2 * C;
-  hipLaunchKernelGGL(colstats_partial_kernel, dim3(nblk), dim3(256), 0, st, in_feats, n_cap, n_dev, row0_dev, C, part);
-  hipLaunchKernelGGL(colstats_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n_cap, n_dev, stats_ws);
+  hipLaunchKernelGGL(colsum_partial_kernel<StatsTerm>, dim3(nblk), dim3(256), 0, st, StatsTerm{in_feats}, n_cap, n_dev, row0_dev, C,
+                     part);
+  hipLaunchKernelGGL(colstats_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n_cap, n_dev, stats_ws, 0.0f, nullptr,
+                     nullptr, nullptr);
   if (out_feats != nullptr)            // NULL: statistics only (cnrma_sparse_instnorm_maxpool_f32 applies them)
     hipLaunchKernelGGL(instnorm_apply_kernel, dim3(grid_for(n_cap * C, 256, 4096)), dim3(256), 0, st, in_feats, n_cap,
                        n_dev, row0_dev, C, stats_ws, weight, bias, eps, relu, out_feats);
@@ -4767,7 +4679,8 @@ extern "C" int cnrma_bn_backward_f32(const float* grad_out, const float* x, int6
   const int nblk = 1024;
   double* sums = ws;                  // [2C]
   double* part = ws + 2 * C;          // [nblk][2C]
-  hipLaunchKernelGGL(colsum2_partial_kernel, dim3(nblk), dim3(256), 0, st, grad_out, x, n, C, part);
+  hipLaunchKernelGGL(colsum_partial_kernel<GradTerm>, dim3(nblk), dim3(256), 0, st, GradTerm{grad_out, x, nullptr, 0}, n, nullptr,
+                     nullptr, C, part);
   hipLaunchKernelGGL(bn_backward_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n, stats, eps, grad_weight,
                      grad_bias, sums);
   hipLaunchKernelGGL(bn_backward_apply_kernel, dim3(grid_for(n * C, 256, 4096)), dim3(256), 0, st, grad_out, x, n, C, stats,
@@ -4789,9 +4702,9 @@ extern "C" int cnrma_bn_train_forward_f32(const float* x, int64_t n, int C, cons
   hipStream_t st = as_stream(stream);
   const int nblk = 1024;
   double* part = stats_ws + 2 * C;
-  hipLaunchKernelGGL(colstats_partial_kernel, dim3(nblk), dim3(256), 0, st, x, n, nullptr, nullptr, C, part);
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n, stats_ws, momentum, running_mean,
-                     running_var, num_batches_tracked);
+  hipLaunchKernelGGL(colsum_partial_kernel<StatsTerm>, dim3(nblk), dim3(256), 0, st, StatsTerm{x}, n, nullptr, nullptr, C, part);
+  hipLaunchKernelGGL(colstats_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n, nullptr, stats_ws, momentum,
+                     running_mean, running_var, num_batches_tracked);
   hipLaunchKernelGGL(bn_apply_kernel, dim3(grid_for(n * C / 4, 256, 4096)), dim3(256), 0, st, x, n, C, stats_ws, weight, bias, eps,
                      residual, relu, out);
   CNRMA_LAUNCH_CHECK();
@@ -4811,7 +4724,8 @@ extern "C" int cnrma_bn_train_backward_f32(const float* grad_out, const float* x
   const int nblk = 1024;
   double* sums = ws;                  // [2C]
   double* part = ws + 2 * C;          // [nblk][2C]
-  hipLaunchKernelGGL(bn_colsum2_partial_kernel, dim3(nblk), dim3(256), 0, st, grad_out, x, y, act, n, C, part);
+  hipLaunchKernelGGL(colsum_partial_kernel<GradTerm>, dim3(nblk), dim3(256), 0, st, GradTerm{grad_out, x, y, act}, n, nullptr, nullptr,
+                     C, part);
   hipLaunchKernelGGL(bn_backward_final_kernel, dim3((unsigned)C), dim3(256), 0, st, part, nblk, C, n, stats, eps, grad_weight,
                      grad_bias, sums);
   hipLaunchKernelGGL(bn_backward_apply2_kernel, dim3(grid_for(n * C / 4, 256, 4096)), dim3(256), 0, st, grad_out, x, y, act, n, C, stats,

@@ -325,3 +325,86 @@ def get_bboxes(head, results):
         boxes.append(decode_boxes(pt, bp, head.yaw_parametrization))
         scores.append(s)
     return torch.cat(boxes), torch.cat(scores)
+
+
+# ---- prepared weight images (csrc/sparse.hip "Prepared weight images"): exact host restatement, byte for byte -------------------
+WEIGHT_IMAGE_KINDS = {            # kind -> (order, encoder)
+    "bf16x3": ("stage", "bf16x3"), "f16": ("stage", "f16x2"), "bf16": ("stage", "bf16"),
+    "f16_frag": ("frag16", "f16x2"), "f32_frag": ("frag32", "f32"), "bf16_frag": ("frag16", "bf16")}
+
+
+def cout_padded(c):
+    """prepared images pad their columns to a multiple of 128 (the largest column tile) with zeros"""
+    return (c + 127) // 128 * 128
+
+
+def _image_order(a, order):
+    """a [K, Ci, Cp] (any dtype) -> [tiles, elements of a tile] in the image's element order; a plane is the rows in sequence.
+    stage:  [K][Ci/32][Cp][32] as one tile (Ci % 32 != 0: plain [K][Cp][Ci]);
+    frag16: tiles [k][slice][column tile], inside [k-step 2][lane 64][j 8], channel 16 k-step + 8 (lane / 32) + j, column lane % 32;
+    frag32: the same tiles, inside [i 4][lane 64][e 4], channel 8 i + 4 (lane / 32) + e, column lane % 32"""
+    K, Ci, Cp = a.shape
+    if order == "stage":
+        if Ci % 32:
+            return a.transpose(0, 2, 1).reshape(1, -1)
+        return a.reshape(K, Ci // 32, 32, Cp).transpose(0, 1, 3, 2).reshape(1, -1)
+    assert Ci % 32 == 0 and Cp % 32 == 0
+    ns, nt = Ci // 32, Cp // 32
+    split = {"frag16": (2, 2, 8), "frag32": (4, 2, 4)}[order]          # channel inside the slice = (step, lane half, element)
+    a = a.reshape(K, ns, *split, nt, 32)                                  # [k][slice][step][half][elem][tile][column]
+    return a.transpose(0, 1, 5, 2, 3, 6, 4).reshape(K * ns * nt, 1024)    # [k][slice][tile] x [step][half][column][elem]
+
+
+def weight_image_index(order, K, Ci, Co):
+    """the flat index into [K][Ci][Co] that element t of one plane of the image holds, -1 for the zero padding"""
+    idx = np.full((K, Ci, cout_padded(Co)), -1, dtype=np.int64)
+    idx[:, :, :Co] = np.arange(K * Ci * Co, dtype=np.int64).reshape(K, Ci, Co)
+    return _image_order(idx, order).reshape(-1)
+
+
+def f16_scale(amax):
+    """2^(14 - e) with amax < 2^e (1 for amax == 0 or not finite): weight * scale stays inside fp16 with headroom, exactly"""
+    amax = np.float32(amax)
+    if not (amax > 0) or not (amax < np.float32(3.0e38)):
+        return np.float32(1.0)
+    e = int(np.frexp(amax)[1])
+    return np.float32(np.ldexp(np.float32(1.0), int(np.clip(14 - e, -100, 100))))
+
+
+def _split3_trunc(a):
+    """fp32 -> three bf16 bit patterns, a == hi + mid + lo exactly: each piece is the top 16 bits of what is left"""
+    out, r = [], a.astype(np.float32)
+    for _ in range(3):
+        top = r.view(np.uint32) & np.uint32(0xFFFF0000)
+        out.append((top >> 16).astype(np.uint16))
+        r = r - top.view(np.float32)
+    return out
+
+
+def weight_image(kind, W, transpose=False, flip=False):
+    """the prepared image `kind` of W fp32 [K, Cin, Cout] as the library writes it, np.uint8: the planes, and for the fp16 kinds the
+    trailer word max|W| behind them.  transpose: of the data gradient's weights W'[k] = W[K - 1 - k if flip else k]^T instead"""
+    order, enc = WEIGHT_IMAGE_KINDS[kind]
+    W = np.ascontiguousarray(np.asarray(W, dtype=np.float32))
+    if transpose:
+        W = np.ascontiguousarray((W[::-1] if flip else W).transpose(0, 2, 1))
+    K, Ci, Co = W.shape
+    idx = weight_image_index(order, K, Ci, Co)
+    v = np.where(idx >= 0, W.reshape(-1)[np.maximum(idx, 0)], np.float32(0)).astype(np.float32)
+    trailer = b""
+    if enc == "f32":
+        planes = [v]
+    elif enc == "bf16":
+        planes = [torch.from_numpy(v).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)]
+    elif enc == "bf16x3":
+        planes = _split3_trunc(v)
+    else:
+        amax = np.abs(W).max() if W.size else np.float32(0)
+        x = v * f16_scale(amax)
+        hi = torch.from_numpy(x).half()
+        lo = (torch.from_numpy(x) - hi.float()).half()
+        planes = [p.view(torch.int16).numpy().view(np.uint16) for p in (hi, lo)]
+        trailer = np.float32(amax).tobytes()
+    tiles = 1 if order == "stage" else len(idx) // 1024                  # planes follow one another inside a tile
+    img = np.stack([p.reshape(tiles, -1) for p in planes], axis=1)
+    return np.frombuffer(img.tobytes() + trailer, dtype=np.uint8)

@@ -182,3 +182,80 @@ def test_fp32_torch_port_matches_the_fp64_oracle():
         np.testing.assert_allclose(b["cls_score"].numpy()[kb][same], a["cls_score"][ka][same], rtol=5e-3, atol=5e-3)
     b32, s32 = ST.get_bboxes(head, r32)
     assert torch.isfinite(b32).all() and torch.isfinite(s32).all()
+
+
+# ---- prepared weight images: the oracle's element orders ----------------------------------------------------------------------
+IMAGE_SHAPES = [(1, 32, 4), (3, 64, 130), (27, 32, 32), (2, 12, 20)]
+
+
+# fragment orders exist for Cin % 32 == 0 only (the entry points reject the rest)
+@pytest.mark.parametrize("order,shape", [(o, s) for o in ("stage", "frag16", "frag32") for s in IMAGE_SHAPES
+                                         if o == "stage" or s[1] % 32 == 0])
+def test_weight_image_order_is_a_bijection_onto_the_padded_weights(order, shape):
+    K, Ci, Co = shape
+    Cp = SO.cout_padded(Co)
+    assert Cp == -(-Co // 128) * 128 and Cp % 128 == 0 and 0 <= Cp - Co < 128
+    idx = SO.weight_image_index(order, K, Ci, Co)
+    assert idx.shape == (K * Ci * Cp,)
+    live = idx[idx >= 0]
+    assert np.array_equal(np.sort(live), np.arange(K * Ci * Co))              # each (k, cin, co < Cout) exactly once
+    assert (idx[idx < 0] == -1).all() and (idx < 0).sum() == K * Ci * (Cp - Co)   # everything else is padding
+    # second statement of the same orders, element by element: the index forms of include/cnrma.h (stage order, fragment tile
+    # shapes) and of the layout comments in csrc/sparse.hip (lane -> channel and column inside a fragment tile); the oracle
+    # builds its orders from reshapes and transposes instead
+    t = np.arange(K * Ci * Cp)
+    if order == "stage" and Ci % 32 == 0:
+        c32, q = t % 32, t // 32
+        co, q = q % Cp, q // Cp
+        cin, k = (q % (Ci // 32)) * 32 + c32, q // (Ci // 32)
+    elif order == "stage":
+        cin, q = t % Ci, t // Ci
+        co, k = q % Cp, q // Cp
+    else:
+        q = t >> 10
+        tile, q = q % (Cp // 32), q // (Cp // 32)
+        sl, k = q % (Ci // 32), q // (Ci // 32)
+        if order == "frag16":
+            j, lane, ks = t & 7, (t >> 3) & 63, (t >> 9) & 1
+            cin = sl * 32 + 16 * ks + 8 * (lane >> 5) + j
+        else:
+            e, lane, i = t & 3, (t >> 2) & 63, (t >> 8) & 3
+            cin = sl * 32 + 8 * i + 4 * (lane >> 5) + e
+        co = tile * 32 + (lane & 31)
+    assert np.array_equal(idx, np.where(co < Co, (k * Ci + cin) * Co + co, -1))
+
+
+@pytest.mark.parametrize("kind", sorted(SO.WEIGHT_IMAGE_KINDS))
+def test_weight_image_encodings_are_exact_and_padding_is_zero(kind):
+    K, Ci, Co = 3, 64, 130
+    order, enc = SO.WEIGHT_IMAGE_KINDS[kind]
+    rng = np.random.default_rng(5)
+    W = rng.standard_normal((K, Ci, Co)).astype(np.float32)
+    img = SO.weight_image(kind, W)
+    idx = SO.weight_image_index(order, K, Ci, Co)
+    n = len(idx)
+    src = np.where(idx >= 0, W.reshape(-1)[np.maximum(idx, 0)], np.float32(0))
+    if enc == "f32":
+        assert np.array_equal(img.view(np.float32), src)
+        return
+    planes = {"bf16": 1, "bf16x3": 3, "f16x2": 2}[enc]
+    body = img[:2 * planes * n].view(np.uint16)
+    body = body.reshape(planes, n) if order == "stage" else body.reshape(-1, planes, 1024).transpose(1, 0, 2).reshape(planes, n)
+    assert (body[:, idx < 0] == 0).all()
+    if enc == "f16x2":
+        assert len(img) == 4 * n + 4 and img[4 * n:].view(np.float32)[0] == np.abs(W).max()
+        scale = SO.f16_scale(np.abs(W).max())
+        assert np.abs(W).max() * scale < 2.0 ** 14 <= np.abs(W).max() * scale * 2
+        hi, lo = (p.view(np.float16).astype(np.float64) for p in body)
+        assert np.abs(hi + lo - src.astype(np.float64) * float(scale)).max() <= 2.0 ** 14 * 2.0 ** -22      # two 11-bit pieces
+    else:
+        pieces = [(p.astype(np.uint32) << 16).view(np.float32).astype(np.float64) for p in body]
+        if enc == "bf16x3":
+            assert np.array_equal(sum(pieces), src.astype(np.float64))                                    # exact split
+        else:
+            assert np.abs(pieces[0] - src).max() <= np.abs(src).max() * 2.0 ** -8
+    # transposed source: the image of W[K - 1 - k]^T
+    W = rng.standard_normal((3, 64, 32)).astype(np.float32)
+    Wt = np.ascontiguousarray(W[::-1].transpose(0, 2, 1))
+    assert np.array_equal(SO.weight_image(kind, W, transpose=True, flip=True), SO.weight_image(kind, Wt))
+    assert not np.array_equal(SO.weight_image(kind, W, transpose=True, flip=False), SO.weight_image(kind, Wt))
