@@ -22,10 +22,18 @@ struct DenseParams {
 };
 
 __device__ __forceinline__ void voxel_world(const DenseParams& p, int64_t g, float* wx, float* wy, float* wz) {
-  const int z = (int)(g % p.Z);
-  const int64_t t = g / p.Z;
-  const int y = (int)(t % p.Y);
-  const int x = (int)(t / p.Y);
+  int x, y, z;
+  if (((uint64_t)g >> 32) == 0) {                // 32-bit divisions wherever the index allows them: a quarter of the 64-bit ones' instructions
+    const unsigned g32 = (unsigned)g, t = g32 / (unsigned)p.Z;
+    z = (int)(g32 - t * (unsigned)p.Z);
+    x = (int)(t / (unsigned)p.Y);
+    y = (int)(t - (unsigned)x * (unsigned)p.Y);
+  } else {
+    z = (int)(g % p.Z);
+    const int64_t t = g / p.Z;
+    y = (int)(t % p.Y);
+    x = (int)(t / p.Y);
+  }
   *wx = (float)x * p.vs + p.ox;  // ray_marching.py:48  (two roundings)
   *wy = (float)y * p.vs + p.oy;
   *wz = (float)z * p.vs + p.oz;
@@ -41,7 +49,13 @@ __device__ __forceinline__ void voxel_world(const DenseParams& p, int64_t g, flo
 // bit-identical): 13.3 -> 10.7 ms; 64 x 64 x 16 slabs 12.8, 32 x 32 x 16 11.5, 16 x 16 x 64 10.8, 8 x 8 x 32 11.5,
 // 128 x 128 x 16 19.0 ms.  A lane of the product kernel stores runs of 4 consecutive z (group_src_lane() below): whole 128-byte
 // lines per store instruction where zi % 4 == 0 and the grid allows it.
-struct SlabOrder { int on, nsx, nsy, nsz, zt, st, tt, zi, nt, own, stagger, groups; };  // zt: z-layers per brick, st: brick side, tt: tile side (columns), zi: inner z run
+struct SlabOrder {
+  int on, nsx, nsy, nsz, zt, st, tt, zi, nt, own, stagger, groups;  // zt: z-layers per brick, st: brick side, tt: tile side (columns), zi: inner z run
+  // p2: st, zt, tt, zi are powers of two and every block index fits 31 bits (the shipped schedule): blocks and threads are
+  // decoded with 32-bit shifts and masks (block_decode(), remap_block()).  lcb = log2(blocks per brick), lzi = log2(zi),
+  // ltt = log2(tt), lzo = log2(zt / zi), ltpr = log2(st / tt)
+  int p2, lcb, lzi, ltt, lzo, ltpr;
+};
 
 __device__ __forceinline__ bool slab_decode(const DenseParams& p, const SlabOrder& o, int64_t gv, int* x, int* y, int* z) {
   const int64_t per = (int64_t)o.st * o.st * o.zt;
@@ -60,6 +74,38 @@ __device__ __forceinline__ bool slab_decode(const DenseParams& p, const SlabOrde
   *y = sy * o.st + (tile % tpr) * o.tt + in % o.tt;
   *z = sz * o.zt + zl;
   return *x < p.X && *y < p.Y && *z < p.Z;
+}
+
+// slab_decode() of thread `tid` of logical block `lb` (voxel lb * 256 + tid).  With o.p2 the same (x, y, z) comes from 32-bit
+// shifts and masks and two 32-bit divisions by the brick counts -- slab_decode()'s 64-bit divisions were most of the ~2200
+// instructions a wave ran before its view loop, in every channel sweep.
+__device__ __forceinline__ bool block_decode(const DenseParams& p, const SlabOrder& o, int64_t lb, int tid, int* x, int* y, int* z) {
+  if (!o.p2) return slab_decode(p, o, lb * 256 + tid, x, y, z);
+  const unsigned b = (unsigned)lb;
+  const unsigned sv = b >> o.lcb;
+  if (sv >= (unsigned)(o.nsx * o.nsy * o.nsz)) return false;
+  const unsigned r = ((b & ((1u << o.lcb) - 1u)) << 8) | (unsigned)tid;
+  const unsigned t = sv / (unsigned)o.nsy, sy = sv - t * (unsigned)o.nsy;
+  const unsigned sz = t / (unsigned)o.nsx, sx = t - sz * (unsigned)o.nsx;
+  const unsigned zin = r & (unsigned)(o.zi - 1), q = r >> o.lzi;
+  const unsigned in = q & ((1u << (2 * o.ltt)) - 1u), q2 = q >> (2 * o.ltt);
+  const unsigned zo = q2 & ((1u << o.lzo) - 1u), tile = q2 >> o.lzo;
+  *x = (int)(sx * o.st + ((tile >> o.ltpr) << o.ltt) + (in >> o.ltt));
+  *y = (int)(sy * o.st + ((tile & ((1u << o.ltpr) - 1u)) << o.ltt) + (in & (unsigned)(o.tt - 1)));
+  *z = (int)(sz * o.zt + ((zo << o.lzi) | zin));
+  return *x < p.X && *y < p.Y && *z < p.Z;
+}
+
+// Launch block -> logical block of the free-running grid: chunk c of `chunk_blocks` blocks belongs to XCD group c % 8 (launch
+// blocks are dealt to the XCDs round-robin).  chunk_blocks <= 0: identity.  o.p2: chunk_blocks == 1 << o.lcb.
+__device__ __forceinline__ int64_t remap_block(unsigned b, int chunk_blocks, const SlabOrder& o) {
+  if (chunk_blocks <= 0) return b;
+  if (o.p2) {
+    const unsigned k = b >> 3;
+    return (((b & 7u) + 8u * (k >> o.lcb)) << o.lcb) | (k & ((1u << o.lcb) - 1u));
+  }
+  const int64_t grp = b & 7, k = b >> 3;
+  return (grp + 8 * (k / chunk_blocks)) * chunk_blocks + k % chunk_blocks;
 }
 
 // Lattice assignment of a brick's z-columns to its workgroups (lockstep schedule; zt == 32, st % 8 == 0): workgroup w of
@@ -188,11 +234,13 @@ __device__ __forceinline__ int group_src_lane(int grp, int vsel) {
 }
 
 typedef float dense_f4 __attribute__((ext_vector_type(4)));
+typedef unsigned int dense_u4 __attribute__((ext_vector_type(4)));
 
-// element type of the feature maps, what one 16-byte gather holds and how many float4 accumulators (Q) it feeds
-template <int ELEM> struct DenseElem { typedef float type; typedef float4 load_t; static constexpr int Q = 1; };
-template <> struct DenseElem<CNRMA_ELEM_F16> { typedef uint16_t type; typedef uint4 load_t; static constexpr int Q = 2; };
-template <> struct DenseElem<CNRMA_ELEM_BF16> { typedef uint16_t type; typedef uint4 load_t; static constexpr int Q = 2; };
+// element type of the feature maps, what one 16-byte gather holds (vec_t: the same as a native vector, the type the gather is
+// loaded as) and how many float4 accumulators (Q) it feeds
+template <int ELEM> struct DenseElem { typedef float type; typedef float4 load_t; typedef dense_f4 vec_t; static constexpr int Q = 1; };
+template <> struct DenseElem<CNRMA_ELEM_F16> { typedef uint16_t type; typedef uint4 load_t; typedef dense_u4 vec_t; static constexpr int Q = 2; };
+template <> struct DenseElem<CNRMA_ELEM_BF16> { typedef uint16_t type; typedef uint4 load_t; typedef dense_u4 vec_t; static constexpr int Q = 2; };
 
 // one 16-byte store of a z-run.  policy 0: plain, 1: non-temporal, 2: sc1 (write-through: the line is not kept in the XCD's L2)
 __device__ __forceinline__ void store_run(float* o, float a, float b, float c, float d, int policy) {
@@ -205,33 +253,52 @@ __device__ __forceinline__ void store_run(float* o, float a, float b, float c, f
 // EPI: 0 direct stores, z-run lane mapping (16-byte stores)   1 LDS-transposed stores   2 direct stores, round-3 lane mapping
 // ELEM: 0 fp32 maps (a lane gathers 4 channels per 16-byte load), CNRMA_ELEM_F16 / CNRMA_ELEM_BF16 16-bit maps (8 channels per
 // 16-byte load, widened exactly and summed in fp32: the same sums as on the widened maps); feat points at elements of that type
+// the voxel of thread `tid` of logical block `lb`: is it in the grid, its world position and its linear index (-1 outside)
+__device__ __forceinline__ bool block_voxel(const DenseParams& p, const SlabOrder& ord, int64_t lb, int tid, float* wx, float* wy,
+                                            float* wz, int64_t* lin) {
+  *wx = 0.f; *wy = 0.f; *wz = 0.f; *lin = -1;
+  bool in_grid;
+  if (ord.on) {
+    int x = 0, y = 0, z = 0;
+    in_grid = ord.on == 2 ? lattice_decode(p, ord, lb, tid, &x, &y, &z) : block_decode(p, ord, lb, tid, &x, &y, &z);
+    if (in_grid) {
+      *lin = ((int64_t)x * p.Y + y) * p.Z + z;
+      *wx = (float)x * p.vs + p.ox; *wy = (float)y * p.vs + p.oy; *wz = (float)z * p.vs + p.oz;      // as voxel_world()
+    }
+  } else {
+    const int64_t g = lb * 256 + tid;
+    in_grid = g < (int64_t)p.X * p.Y * p.Z;
+    if (in_grid) { voxel_world(p, g, wx, wy, wz); *lin = g; }
+  }
+  return in_grid;
+}
+
+// View masks.  At the north-star shape 68 % of the (wave, view) pairs are empty -- none of the wave's 64 voxels projects into the
+// view --, and an empty view step still costs a whole projection (42 vector instructions), repeated identically in each of the 8
+// channel sweeps.  The first sweep, launched on its own, therefore records what it finds out anyway: wave w of logical block lb
+// writes one 64-bit word per 64 views at vmask[(lb * 4 + w) * ceil(V / 64)], bit v % 64 of word v / 64 set iff its ballot
+// "any lane valid" was non-zero for view v.  The other sweeps -- a second launch on the same stream, same grid in x, same block
+// remap, same voxel decode, same project() on the same lanes -- walk the set bits only.  Every word they read was written by the
+// first launch (a wave outside the grid writes nothing and reads nothing), so the table needs no clearing.
+// vmask: the table to walk (PIPE == 1 only), or NULL: every view is walked; vmask_out: the table to record into, or NULL
 template <int LPV, int PIPE, int EPI, int ELEM = 0>
 __device__ __forceinline__ void accum_block(const DenseParams& p, const typename DenseElem<ELEM>::type* __restrict__ feat,
                                             const float* __restrict__ proj, float* __restrict__ volume,
                                             int32_t* __restrict__ count, int64_t lb, int c0, bool write_count,
-                                            const SlabOrder& ord, float* __restrict__ lds_wave, int tid) {
+                                            const SlabOrder& ord, float* __restrict__ lds_wave, int tid,
+                                            const unsigned long long* __restrict__ vmask = nullptr,
+                                            unsigned long long* __restrict__ vmask_out = nullptr) {
   constexpr int VPG = 64 / LPV;
   constexpr int Q = DenseElem<ELEM>::Q, CPL = 4 * Q;        // float4 accumulators / channels per lane and voxel
   typedef typename DenseElem<ELEM>::type feat_t;
   typedef typename DenseElem<ELEM>::load_t load_t;
+  typedef typename DenseElem<ELEM>::vec_t vec_t;
   static_assert(EPI != 1 || ELEM == 0, "the LDS-transposed epilogue exists for fp32 maps only");
   const int64_t G = (int64_t)p.X * p.Y * p.Z;
   const int lane = tid & 63;
-  const int64_t g = lb * 256 + tid;
-  float wx = 0.f, wy = 0.f, wz = 0.f;
-  bool in_grid;
-  int64_t lin = -1;
-  if (ord.on) {
-    int x = 0, y = 0, z = 0;
-    in_grid = ord.on == 2 ? lattice_decode(p, ord, lb, tid, &x, &y, &z) : slab_decode(p, ord, g, &x, &y, &z);
-    if (in_grid) {
-      lin = ((int64_t)x * p.Y + y) * p.Z + z;
-      wx = (float)x * p.vs + p.ox; wy = (float)y * p.vs + p.oy; wz = (float)z * p.vs + p.oz;      // as voxel_world()
-    }
-  } else {
-    in_grid = g < G;
-    if (in_grid) { voxel_world(p, g, &wx, &wy, &wz); lin = g; }
-  }
+  float wx, wy, wz;
+  int64_t lin;
+  bool in_grid = block_voxel(p, ord, lb, tid, &wx, &wy, &wz, &lin);
   if (__ballot(in_grid) == 0ull) return;
   float4 acc[LPV * Q];
 #pragma unroll
@@ -247,13 +314,22 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const typename
     return ok ? ((int)ry * p.W + (int)rx) : -1;
   };
   auto gather = [&](int v, int pix, load_t* q) {
+    // All LPV shuffles first, then LPV loads from the GLOBAL address space.  The maps' address may come out of memory (by
+    // reference), so the compiler took the pointer for a generic one and gathered with flat loads, which count in lgkmcnt like
+    // the shuffles: each load then sat behind a wait that also covered the flat loads before it.  Now the waits between
+    // shuffles and loads count shuffles only and the loads are global_load_dwordx4 with nothing but vmcnt on them.
     const feat_t* fv = fbase + v * plane;
+    int pq[LPV];
+#pragma unroll
+    for (int grp = 0; grp < LPV; ++grp) pq[grp] = __shfl(pix, group_src_lane<LPV, EPI>(grp, vsel), 64);
 #pragma unroll
     for (int grp = 0; grp < LPV; ++grp) {
-      const int pq = __shfl(pix, group_src_lane<LPV, EPI>(grp, vsel), 64);
       if constexpr (ELEM == 0) q[grp] = make_float4(0.f, 0.f, 0.f, 0.f);
       else q[grp] = make_uint4(0u, 0u, 0u, 0u);             // +0.0 in either 16-bit type
-      if (pq >= 0) q[grp] = *reinterpret_cast<const load_t*>(fv + (int64_t)pq * p.C);
+      if (pq[grp] >= 0) {
+        const vec_t t = *(const __attribute__((address_space(1))) vec_t*)(fv + (int64_t)pq[grp] * p.C);
+        q[grp].x = t.x; q[grp].y = t.y; q[grp].z = t.z; q[grp].w = t.w;
+      }
     }
   };
   auto add = [&](const load_t* q) {
@@ -271,15 +347,48 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const typename
   };
 
   if constexpr (PIPE == 1) {
-    int pix_n = pixel_of(0);
-    for (int v = 0; v < p.V; ++v) {
+    // The views to walk, 64 per word: the wave's words of the first sweep's table (scalar loads: the address is wave-uniform), or
+    // all views without a table.  A view whose bit is clear has no valid lane in this wave -- the bit is the ballot of the very
+    // pixel_of() below on these lanes --, so skipping it changes no sum, no count and no order.  All of this is scalar work.
+    const int nw = (p.V + 63) >> 6;
+    const int64_t wave_words = (lb * 4 + __builtin_amdgcn_readfirstlane(tid >> 6)) * nw;
+    const unsigned long long* wm = vmask != nullptr ? vmask + wave_words : nullptr;
+    unsigned long long seen = 0ull;                        // recording: the views of the current word with a valid lane
+    auto word = [&](int w) -> unsigned long long {
+      if (wm != nullptr) return wm[w];
+      const int left = p.V - 64 * w;
+      return left >= 64 ? ~0ull : (1ull << left) - 1ull;
+    };
+    int w = 0;
+    unsigned long long m = word(0);
+    auto next_view = [&]() -> int {                        // the next set bit, -1 after the last
+      while (m == 0ull) {
+        if (++w >= nw) return -1;
+        m = word(w);
+      }
+      const int v = 64 * w + __builtin_ctzll(m);
+      m &= m - 1ull;
+      return v;
+    };
+    int v = next_view();
+    int pix_n = v >= 0 ? pixel_of(v) : -1;
+    while (v >= 0) {
       const int pix = pix_n;
       const bool any = __ballot(pix >= 0) != 0ull;
       load_t q[LPV];
       if (any) gather(v, pix, q);
       cnt += pix >= 0 ? 1 : 0;
-      pix_n = (v + 1 < p.V) ? pixel_of(v + 1) : -1;        // overlaps with the gathers in flight
+      const int vn = next_view();
+      if (vmask_out != nullptr) {                          // recording walks every view, so every word is met and written
+        if (any) seen |= 1ull << (v & 63);
+        if (vn < 0 || (vn >> 6) != (v >> 6)) {
+          if (lane == 0) vmask_out[wave_words + (v >> 6)] = seen;
+          seen = 0ull;
+        }
+      }
+      pix_n = vn >= 0 ? pixel_of(vn) : -1;                 // overlaps with the gathers in flight
       if (any) add(q);
+      v = vn;
     }
   } else {
     // two views in flight: q0 holds view v (issued one iteration ago), q1 is issued for view v + 1 before q0 is consumed
@@ -312,7 +421,7 @@ __device__ __forceinline__ void accum_block(const DenseParams& p, const typename
     int x = 0, y = 0, z = 0;
     const int64_t g2 = lb * 256 + t2;
     bool in2;
-    if (ord.on) in2 = ord.on == 2 ? lattice_decode(p, ord, lb, t2, &x, &y, &z) : slab_decode(p, ord, g2, &x, &y, &z);
+    if (ord.on) in2 = ord.on == 2 ? lattice_decode(p, ord, lb, t2, &x, &y, &z) : block_decode(p, ord, lb, t2, &x, &y, &z);
     else { in2 = g2 < G; z = (int)(g2 % p.Z); y = (int)((g2 / p.Z) % p.Y); x = (int)(g2 / p.Z / p.Y); }
     in_grid = in2;
     lin = in2 ? ((int64_t)x * p.Y + y) * p.Z + z : -1;
@@ -420,7 +529,9 @@ __global__ __launch_bounds__(256, PIPE == 1 ? 4 : 3) void backproject_accum_pipe
                                                                      int32_t* __restrict__ count, int chunk_blocks,
                                                                      int64_t n_phys, SlabOrder ord,
                                                                      unsigned int* __restrict__ bar,
-                                                                     const float* const* __restrict__ feat_ref) {
+                                                                     const float* const* __restrict__ feat_ref,
+                                                                     const unsigned long long* __restrict__ vmask,
+                                                                     unsigned long long* __restrict__ vmask_out, int sweep0) {
   // feat_ref != NULL: the feature maps are handed over BY REFERENCE -- a device word holds their address (one scalar load);
   // a captured launch sequence can then read whatever tensor the producer wrote, with no copy into a static buffer
   if (feat_ref != nullptr) feat = *feat_ref;
@@ -451,18 +562,15 @@ __global__ __launch_bounds__(256, PIPE == 1 ? 4 : 3) void backproject_accum_pipe
       }
   } else {
     int64_t lb = blockIdx.x;
-    int sweep = blockIdx.y;
+    int sweep = blockIdx.y + sweep0;                     // sweep0: first channel sweep of this launch
     if (ord.own > 0) {
       // one channel sweep per XCD group (8 sweeps <-> 8 groups): every group walks ALL bricks in order for its own 128-byte
       // slice of the pixel rows, so the workgroups resident on an XCD are one contiguous run of neighbouring bricks (not
       // every 8th brick) and no feature line is fetched by two XCDs (dense_l2sim: read hit rate 34 % -> 41 %)
       sweep = (int)(lb & 7);
       lb >>= 3;
-    } else if (chunk_blocks > 0) {
-      const int64_t grp = lb & 7, k = lb >> 3;
-      lb = (grp + 8 * (k / chunk_blocks)) * chunk_blocks + k % chunk_blocks;
-    }
-    accum_block<LPV, PIPE, EPI>(p, feat, proj, volume, count, lb, sweep * (4 * LPV), sweep == 0, ord, lds_wave, (int)threadIdx.x);
+    } else lb = remap_block(blockIdx.x, chunk_blocks, ord);
+    accum_block<LPV, PIPE, EPI>(p, feat, proj, volume, count, lb, sweep * (4 * LPV), sweep == 0, ord, lds_wave, (int)threadIdx.x, vmask, vmask_out);
   }
 }
 
@@ -475,15 +583,13 @@ __global__ __launch_bounds__(256, OCC) void backproject_accum_h16_kernel(DensePa
                                                                          float* __restrict__ volume,
                                                                          int32_t* __restrict__ count, int chunk_blocks,
                                                                          SlabOrder ord,
-                                                                         const uint16_t* const* __restrict__ feat_ref) {
+                                                                         const uint16_t* const* __restrict__ feat_ref,
+                                                                         const unsigned long long* __restrict__ vmask,
+                                                                         unsigned long long* __restrict__ vmask_out, int sweep0) {
   if (feat_ref != nullptr) feat = *feat_ref;               // by reference, as backproject_accum_pipe_kernel
-  int64_t lb = blockIdx.x;
-  if (chunk_blocks > 0) {
-    const int64_t grp = lb & 7, k = lb >> 3;
-    lb = (grp + 8 * (k / chunk_blocks)) * chunk_blocks + k % chunk_blocks;
-  }
-  const int sweep = blockIdx.y;
-  accum_block<LPV, 1, 0, ELEM>(p, feat, proj, volume, count, lb, sweep * (8 * LPV), sweep == 0, ord, nullptr, (int)threadIdx.x);
+  const int64_t lb = remap_block(blockIdx.x, chunk_blocks, ord);
+  const int sweep = blockIdx.y + sweep0;
+  accum_block<LPV, 1, 0, ELEM>(p, feat, proj, volume, count, lb, sweep * (8 * LPV), sweep == 0, ord, nullptr, (int)threadIdx.x, vmask, vmask_out);
 }
 
 #ifdef CNRMA_EXPERIMENTS
@@ -519,9 +625,30 @@ static constexpr DenseTune k_dense_tune{};
 #define CNRMA_DENSE_TUNE k_dense_tune
 #endif
 
+// the shift fields of a brick order whose sizes are powers of two, for a grid of gx blocks in chunks of cb blocks (remap_block()
+// shifts by lcb, so the chunk must be exactly one brick)
+static void slab_shifts(SlabOrder& o, int64_t gx, int64_t cb) {
+  auto lg = [](int v) { int l = 0; while (l < 30 && (1 << l) < v) ++l; return (1 << l) == v ? l : -1; };
+  const int lst = lg(o.st), lzt = lg(o.zt), ltt = lg(o.tt), lzi = lg(o.zi);
+  if (lst < 0 || lzt < 0 || ltt < 0 || lzi < 0 || 2 * lst + lzt < 8 || gx >= ((int64_t)1 << 31) ||
+      cb != ((int64_t)1 << (2 * lst + lzt - 8))) return;
+  o.p2 = 1; o.lcb = 2 * lst + lzt - 8; o.lzi = lzi; o.ltt = ltt; o.lzo = lzt - lzi; o.ltpr = lst - ltt;
+}
+
+// The caller's workspace behind its first CNRMA_DENSE_WORKSPACE_BYTES as the view-mask table of a grid of gx blocks, or NULL (then
+// one launch walks every view in every sweep, as it did before the table existed): the workspace must hold CNRMA_DENSE_MASK_BYTES behind the
+// counters, and the table of this grid -- one word per wave and 64 views -- must fit into that.
+static unsigned long long* view_mask_table(const DenseParams& p, void* workspace, int64_t workspace_bytes, int64_t gx) {
+  const int64_t room = CNRMA_DENSE_MASK_BYTES(p.X, p.Y, p.Z, p.V);
+  if (workspace == nullptr || (reinterpret_cast<uintptr_t>(workspace) & 7) != 0 || workspace_bytes < CNRMA_DENSE_WORKSPACE_BYTES + room) return nullptr;
+  if (gx * 4 * ((p.V + 63) / 64) * 8 > room) return nullptr;
+  return reinterpret_cast<unsigned long long*>(static_cast<char*>(workspace) + CNRMA_DENSE_WORKSPACE_BYTES);
+}
+
 template <int LPV>
 int launch_accum_coop(const DenseParams& p, const float* feat, const float* proj, float* volume, int32_t* count,
-                      unsigned int* bar, hipStream_t st, const float* const* feat_ref = nullptr) {
+                      void* workspace, int64_t workspace_bytes, hipStream_t st, const float* const* feat_ref = nullptr) {
+  unsigned int* bar = (workspace != nullptr && workspace_bytes >= CNRMA_DENSE_WORKSPACE_BYTES) ? static_cast<unsigned int*>(workspace) : nullptr;
   const DenseTune t = CNRMA_DENSE_TUNE;
   if (feat_ref != nullptr && t.variant != 1) return CNRMA_EINVAL;      // by-reference hand-off: the product kernel only
   const int64_t G = (int64_t)p.X * p.Y * p.Z;
@@ -541,6 +668,7 @@ int launch_accum_coop(const DenseParams& p, const float* feat, const float* proj
   int64_t gx = nb;
   if (cb > 0 && (nb >= 16 * cb || ord.on)) gx = ceil_div(ceil_div(nb, cb), 8) * 8 * cb;      // whole chunks for every XCD group
   else cb = 0;
+  if (ord.on) slab_shifts(ord, gx, cb);
 #ifdef CNRMA_EXPERIMENTS
   if (t.variant == 0) {
     int64_t launch_x = gx;
@@ -569,26 +697,33 @@ int launch_accum_coop(const DenseParams& p, const float* feat, const float* proj
   const int n_sweeps = (int)ceil_div(p.C, 4 * LPV);
   if (t.own && !lock && ord.on && n_sweeps == 8 && nb * 8 < ((int64_t)1 << 31)) ord.own = 1;
   dim3 grid(lock ? (unsigned)(ord.groups * cb) : (ord.own ? (unsigned)(nb * 8) : (unsigned)gx), (lock || ord.own) ? 1u : (unsigned)n_sweeps);
+  // the free-running grid with one view in flight and more than one sweep: the first sweep records the view masks, the others walk
+  // them -- when the caller's workspace has room for the table
+  unsigned long long* vmask = (!lock && !ord.own && t.pipe != 2 && n_sweeps > 1) ? view_mask_table(p, workspace, workspace_bytes, gx) : nullptr;
+  auto launch = [&](dim3 grid, int sweep0, const unsigned long long* vin, unsigned long long* vout) -> int {
 #ifdef CNRMA_EXPERIMENTS
 #define CNRMA_DENSE_LAUNCH(PIPE, EPI)                                                                                      \
   do {                                                                                                                     \
     if (lock)                                                                                                              \
       hipLaunchKernelGGL((backproject_accum_pipe_kernel<LPV, PIPE, EPI, 1>), grid, dim3(256), 0, st, p, feat, proj, volume, \
-                         count, (int)cb, gx, ord, bar, feat_ref);                                                          \
+                         count, (int)cb, gx, ord, bar, feat_ref, vin, vout, sweep0);                                       \
     else                                                                                                                   \
       hipLaunchKernelGGL((backproject_accum_pipe_kernel<LPV, PIPE, EPI, 0>), grid, dim3(256), (size_t)t.ldspad * 1024, st, p,  \
-                         feat, proj, volume, count, (int)cb, gx, ord, bar, feat_ref);                                     \
+                         feat, proj, volume, count, (int)cb, gx, ord, bar, feat_ref, vin, vout, sweep0);                  \
   } while (0)
   if (t.pipe == 2) { if (t.epi) CNRMA_DENSE_LAUNCH(2, 1); else if (t.zrun) CNRMA_DENSE_LAUNCH(2, 0); else CNRMA_DENSE_LAUNCH(2, 2); }
   else             { if (t.epi) CNRMA_DENSE_LAUNCH(1, 1); else if (t.zrun) CNRMA_DENSE_LAUNCH(1, 0); else CNRMA_DENSE_LAUNCH(1, 2); }
 #undef CNRMA_DENSE_LAUNCH
 #else                                   // the product schedule: one view in flight per wave, direct 16-byte stores of z-runs, free-running grid
-  (void)lock;
   hipLaunchKernelGGL((backproject_accum_pipe_kernel<LPV, 1, 0, 0>), grid, dim3(256), 0, st, p, feat, proj, volume, count, (int)cb, gx,
-                     ord, bar, feat_ref);
+                     ord, bar, feat_ref, vin, vout, sweep0);
 #endif
-  CNRMA_LAUNCH_CHECK();
-  return 0;
+    CNRMA_LAUNCH_CHECK();
+    return 0;
+  };
+  if (vmask == nullptr) return launch(grid, 0, nullptr, nullptr);
+  const int rc = launch(dim3(grid.x, 1u), 0, nullptr, vmask);
+  return rc != 0 ? rc : launch(dim3(grid.x, (unsigned)(n_sweeps - 1)), 1, vmask, nullptr);
 }
 
 __global__ __launch_bounds__(256) void backproject_index_kernel(DenseParams p, const float* __restrict__ proj,
@@ -637,16 +772,15 @@ static int backproject_accum_any(const float* feat_nhwc, const float* const* fea
   if (V <= 0 || C <= 0 || H <= 0 || W <= 0 || X <= 0 || Y <= 0 || Z <= 0) return CNRMA_EINVAL;
   DenseParams p{V, C, H, W, X, Y, Z, voxel_size, ox, oy, oz};
   hipStream_t st = as_stream(stream);
-  unsigned int* bar = (workspace != nullptr && workspace_bytes >= CNRMA_DENSE_WORKSPACE_BYTES) ? static_cast<unsigned int*>(workspace) : nullptr;
 #ifdef CNRMA_EXPERIMENTS                // lanes per voxel by hand: the 16-lane form exists in the experiments library only
   const int l = CNRMA_DENSE_TUNE.lpv;
-  if (l == 16 && C % 64 == 0) return launch_accum_coop<16>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
-  if (l == 4 && C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
+  if (l == 16 && C % 64 == 0) return launch_accum_coop<16>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
+  if (l == 4 && C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
 #endif
-  if (C % 32 == 0) return launch_accum_coop<8>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
-  if (C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
-  if (C % 8 == 0) return launch_accum_coop<2>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
-  if (C % 4 == 0) return launch_accum_coop<1>(p, feat_nhwc, proj, volume, count, bar, st, feat_ref);
+  if (C % 32 == 0) return launch_accum_coop<8>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
+  if (C % 16 == 0) return launch_accum_coop<4>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
+  if (C % 8 == 0) return launch_accum_coop<2>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
+  if (C % 4 == 0) return launch_accum_coop<1>(p, feat_nhwc, proj, volume, count, workspace, workspace_bytes, st, feat_ref);
   if (feat_ref != nullptr) return CNRMA_EINVAL;
   return launch_accum<1>(p, feat_nhwc, proj, volume, count, st);
 }
@@ -679,28 +813,34 @@ extern "C" int cnrma_backproject_accum_ref_f32(const float* const* feat_nhwc_ref
 
 template <int LPV, int OCC>
 static int launch_accum_h16(const DenseParams& p, const uint16_t* feat, const uint16_t* const* feat_ref, int elem, const float* proj,
-                            float* volume, int32_t* count, hipStream_t st) {
+                            float* volume, int32_t* count, void* workspace, int64_t workspace_bytes, hipStream_t st) {
   constexpr DenseTune t{};
   SlabOrder ord{1, (int)ceil_div(p.X, t.st), (int)ceil_div(p.Y, t.st), (int)ceil_div(p.Z, t.zt), t.zt, t.st, t.tt, t.zi, t.nt, 0, 0, 8};
   const int64_t cb = (int64_t)t.st * t.st * t.zt / 256;                  // one brick per chunk
   const int64_t nb = (int64_t)ord.nsx * ord.nsy * ord.nsz * cb;
   const int64_t gx = ceil_div(ceil_div(nb, cb), 8) * 8 * cb;             // whole chunks for every XCD group
-  dim3 grid((unsigned)gx, (unsigned)ceil_div(p.C, 8 * LPV));
-  if (elem == CNRMA_ELEM_F16)
-    hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_F16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
-                       (int)cb, ord, feat_ref);
-  else
-    hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_BF16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
-                       (int)cb, ord, feat_ref);
-  CNRMA_LAUNCH_CHECK();
-  return 0;
+  slab_shifts(ord, gx, cb);
+  const int n_sweeps = (int)ceil_div(p.C, 8 * LPV);
+  unsigned long long* vmask = n_sweeps > 1 ? view_mask_table(p, workspace, workspace_bytes, gx) : nullptr;      // as launch_accum_coop
+  auto launch = [&](dim3 grid, int sweep0, const unsigned long long* vin, unsigned long long* vout) -> int {
+    if (elem == CNRMA_ELEM_F16)
+      hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_F16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
+                         (int)cb, ord, feat_ref, vin, vout, sweep0);
+    else
+      hipLaunchKernelGGL((backproject_accum_h16_kernel<LPV, CNRMA_ELEM_BF16, OCC>), grid, dim3(256), 0, st, p, feat, proj, volume, count,
+                         (int)cb, ord, feat_ref, vin, vout, sweep0);
+    CNRMA_LAUNCH_CHECK();
+    return 0;
+  };
+  if (vmask == nullptr) return launch(dim3((unsigned)gx, (unsigned)n_sweeps), 0, nullptr, nullptr);
+  const int rc = launch(dim3((unsigned)gx, 1u), 0, nullptr, vmask);
+  return rc != 0 ? rc : launch(dim3((unsigned)gx, (unsigned)(n_sweeps - 1)), 1, vmask, nullptr);
 }
 
 extern "C" int cnrma_backproject_accum_h16(const void* feat_nhwc, const void* const* feat_nhwc_ref, int elem, const float* proj,
                                            int V, int C, int H, int W, int X, int Y, int Z, float voxel_size, float ox, float oy,
                                            float oz, float* volume, int32_t* count, void* workspace, int64_t workspace_bytes,
                                            void* stream) {
-  (void)workspace; (void)workspace_bytes;                  // the lockstep schedules that use it have no 16-bit form
   if (!elem16_known(elem) || (feat_nhwc == nullptr) == (feat_nhwc_ref == nullptr) || (reinterpret_cast<uintptr_t>(feat_nhwc) & 15) != 0)
     return CNRMA_EINVAL;
   if (V <= 0 || C <= 0 || C % 8 != 0 || H <= 0 || W <= 0 || X <= 0 || Y <= 0 || Z <= 0) return CNRMA_EINVAL;
@@ -713,11 +853,11 @@ extern "C" int cnrma_backproject_accum_h16(const void* feat_nhwc, const void* co
 #ifdef CNRMA_EXPERIMENTS                // either C % 64 == 0 form by hand, for A/B runs (scripts/dense_half_ab.py)
   if (CNRMA_DENSE_TUNE.lpv == 8 || CNRMA_DENSE_TUNE.lpv == 4) lanes64 = CNRMA_DENSE_TUNE.lpv;
 #endif
-  if (C % 64 == 0 && lanes64 == 8) return launch_accum_h16<8, 3>(p, f, fr, elem, proj, volume, count, st);
+  if (C % 64 == 0 && lanes64 == 8) return launch_accum_h16<8, 3>(p, f, fr, elem, proj, volume, count, workspace, workspace_bytes, st);
 #endif
-  if (C % 32 == 0) return launch_accum_h16<4, 4>(p, f, fr, elem, proj, volume, count, st);
-  if (C % 16 == 0) return launch_accum_h16<2, 4>(p, f, fr, elem, proj, volume, count, st);
-  return launch_accum_h16<1, 4>(p, f, fr, elem, proj, volume, count, st);
+  if (C % 32 == 0) return launch_accum_h16<4, 4>(p, f, fr, elem, proj, volume, count, workspace, workspace_bytes, st);
+  if (C % 16 == 0) return launch_accum_h16<2, 4>(p, f, fr, elem, proj, volume, count, workspace, workspace_bytes, st);
+  return launch_accum_h16<1, 4>(p, f, fr, elem, proj, volume, count, workspace, workspace_bytes, st);
 }
 
 // Backward of the accumulate + mean w.r.t. the feature maps (training): volume[c][g] = sum_v feat[v][pix_v(g)][c] / count[g],

@@ -497,6 +497,14 @@ class StaticScene:
                 if torch.is_tensor(t) and t.is_cuda:
                     t.record_stream(self.stream)
 
+    def _dense_workspace(self):
+        """this scene's own workspace of the dense kernel (arrival counters + view masks): the captured graph replays into it, so
+        it lives as long as the scene"""
+        if getattr(self, "_dense_ws", None) is None:
+            self._dense_ws = rma.dense_workspace(self.device, self.cfg.dims, self.shape_nhwc[0], self.shape_nhwc[3],
+                                                 self.feature_dtype in rma.ELEM_CODES)
+        return self._dense_ws
+
     # ---- the launch sequence ---------------------------------------------------------------------------------------
     def _trace(self):
         cfg, plan = self.cfg, self.plan
@@ -518,7 +526,8 @@ class StaticScene:
                     out["volume"], out["count"] = rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin,
                                                                         cfg.stride, proj_scaled=self.proj_scaled,
                                                                         feat_ref=self.feat_ref, shape=self.shape_nhwc,
-                                                                        feat_dtype=self.feature_dtype)
+                                                                        feat_dtype=self.feature_dtype,
+                                                                        workspace=self._dense_workspace())
             fixed = cfg.sample_seed is not None          # a fixed seed: every replay draws the same subset (as forward_scene)
             coords, feats, n_sel, info = rma.aggregate_points_static(
                 self.nhwc, self.proj_inv, self.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
@@ -756,7 +765,8 @@ class StaticBatch:
             for b, h in enumerate(self.holders):                  # the geometric half, scene by scene
                 if self.dense:
                     vols.append(rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin, cfg.stride,
-                                                      proj_scaled=h.proj_scaled, feat_ref=h.feat_ref, shape=h.shape_nhwc))
+                                                      proj_scaled=h.proj_scaled, feat_ref=h.feat_ref, shape=h.shape_nhwc,
+                                                      workspace=h._dense_workspace()))
                 coords, feats, n_sel, info = rma.aggregate_points_static(
                     h.nhwc, h.proj_inv, h.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
                     max_points=cfg.max_points, seed=(cfg.sample_seed if fixed else 0x5EED) + 7919 * b * (0 if fixed else 1),

@@ -86,7 +86,7 @@ def is_channels_last(features, dtypes=(torch.float32,)):
 
 
 def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stride, proj_scaled=None, feat_ref=None, shape=None,
-                      feat_dtype=torch.float32):
+                      feat_dtype=torch.float32, workspace=None):
     """Dense unprojection of all views + mean (ray_marching.py:21-69, :220-257) in one kernel.
 
     features_nhwc [V,H,W,C] device fp32, fp16 or bf16; projections [V,3,4] full-resolution (scaled here by `stride`), or
@@ -94,6 +94,8 @@ def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stri
     16-bit maps are read in place (cnrma_backproject_accum_h16; bit-identical to the fp32 kernel on `features_nhwc.float()`)
     when C % 8 == 0 and their base is 16-byte aligned; otherwise they are widened first -- the result is the same.  By
     reference (feat_ref), `feat_dtype` names the element type of the maps behind the address.
+    workspace: the caller's own dense_workspace(...) -- what a captured launch sequence passes, so that the block its graph
+    replays into lives as long as the graph; by default the block kept per (device, stream).
     Returns volume [C,X,Y,Z] fp32 (mean over the views that see the voxel, 0 elsewhere) and count [X,Y,Z] int32;
     the reference's `valid` is `count > 0`.
     """
@@ -110,7 +112,8 @@ def backproject_accum(features_nhwc, projections, dims, voxel_size, origin, stri
     volume = torch.empty((C, X, Y, Z), dtype=torch.float32, device=dev)
     count = torch.empty((X, Y, Z), dtype=torch.int32, device=dev)
     st = stream()
-    ws = _dense_workspace(dev, st)
+    h16 = feat_dtype in ELEM_CODES if feat_ref is not None else _h16_readable(features_nhwc)
+    ws = workspace if workspace is not None else _dense_workspace(dev, st, dense_workspace_bytes(dims, V, C, h16))
     tail = (ptr(proj), V, C, H, W, X, Y, Z, float(voxel_size), float(origin[0]), float(origin[1]), float(origin[2]), ptr(volume),
             ptr(count), ptr(ws), ws.numel() * 4, st)
     if feat_ref is not None:
@@ -131,16 +134,54 @@ _DENSE_WS = {}
 _DENSE_KEYS = ("variant", "slab", "st", "zt", "tt", "zi", "chunk", "persist", "lpv", "pipe", "epi", "lockstep", "lattice", "nt", "own", "stagger", "groups", "ldspad", "zrun")
 
 
-def _dense_workspace(dev, st):
-    """arrival counters of the dense kernel's lockstep schedules (debug / A-B only; the product schedule ignores them):
-    one zeroed block per (device, stream).  The counters are monotonic -- never reset -- so calls on one stream simply
-    keep counting"""
-    key = (dev.index if dev.index is not None else torch.cuda.current_device(), st)
+DENSE_WORKSPACE_BYTES = 1024     # CNRMA_DENSE_WORKSPACE_BYTES of include/cnrma.h
+DENSE_MASK_MIN_SWEEPS = 3        # channel sweeps from which on the callers here give the dense kernel room for its view masks.  The
+                                 # masked form launches sweep 0 on its own (it records the masks) and the other sweeps behind it.
+                                 # Kernel alone, medians of six rounds, masked / every view walked ("per-wave view
+                                 # masks"; profiles/r11_dense_mask_ab_*.log): 8 sweeps 9.07 / 9.58 ms, 4 sweeps 3.29 / 3.60, 3 sweeps
+                                 # 2.50 / 2.71 -- more than the spread of either series; 2 sweeps 1.77 / 1.85, inside the spread:
+                                 # two sweeps keep the single launch, and one sweep has no second sweep to gain from
+
+
+def dense_mask_bytes(dims, V):
+    """CNRMA_DENSE_MASK_BYTES(X, Y, Z, V) of include/cnrma.h: room for the dense kernel's per-wave view masks"""
+    X, Y, Z = dims
+    return (((X + 31) // 32) * ((Y + 31) // 32) * ((Z + 31) // 32) + 7) * 512 * ((V + 63) // 64) * 8
+
+
+def dense_sweeps(C, h16=False):
+    """channel sweeps of the dense kernel (csrc/dense.hip: 4 channels per lane of fp32 maps, 8 of 16-bit maps; lanes per voxel by
+    channel count)"""
+    if h16:
+        return -(-C // (8 * (4 if C % 32 == 0 else 2 if C % 16 == 0 else 1)))
+    return -(-C // (4 * (8 if C % 32 == 0 else 4 if C % 16 == 0 else 2 if C % 8 == 0 else 1)))
+
+
+def dense_workspace_bytes(dims, V, C=None, h16=False):
+    """bytes of workspace to hand the dense kernel: the counters, and room for the view masks where they pay (C = None: always)"""
+    masks = C is None or dense_sweeps(C, h16) >= DENSE_MASK_MIN_SWEEPS
+    return DENSE_WORKSPACE_BYTES + (dense_mask_bytes(dims, V) if masks else 0)
+
+
+def dense_workspace(dev, dims, V, C=None, h16=False):
+    """a zeroed workspace block of the dense kernel for grids up to `dims` and `V` views, owned by the caller: one per call in
+    flight (sized by dense_workspace_bytes)"""
+    return torch.zeros((dense_workspace_bytes(dims, V, C, h16) + 3) // 4, dtype=torch.int32, device=dev)
+
+
+def _dense_workspace(dev, st, nbytes=0):
+    """the dense kernel's workspace, one zeroed block per (device, stream, size): DENSE_WORKSPACE_BYTES of arrival counters for
+    the lockstep schedules (debug / A-B only; monotonic -- never reset --, so calls on one stream simply keep counting) and,
+    when `nbytes` asks for it, room behind them for the view masks (written by the first channel sweep of every call before the
+    other sweeps read them, so calls on one stream share them too).  A block is never resized: a captured graph keeps replaying into the block it
+    was captured with."""
+    nbytes = max(int(nbytes), DENSE_WORKSPACE_BYTES)
+    key = (dev.index if dev.index is not None else torch.cuda.current_device(), st, nbytes)
     ws = _DENSE_WS.get(key)
     if ws is None:
         if len(_DENSE_WS) >= 64:                  # streams come and go; their handles are all this table knows of them
             _DENSE_WS.pop(next(iter(_DENSE_WS)))
-        ws = torch.zeros(256, dtype=torch.int32, device=dev)
+        ws = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev)
         _DENSE_WS[key] = ws
     return ws
 

@@ -56,12 +56,26 @@ int cnrma_nchw_to_nhwc_f32(const float* feat_nchw, float* feat_nhwc, int V, int 
  *           clear_3d_features()      ray_marching.py:247-257   (divide by count, zero unseen voxels)
  * proj[V][3][4]: rows 0-1 already divided by backbone2d_stride (ray_marching.py:238-239).
  * volume[C][X][Y][Z] (mean, 0 where count == 0), count[X][Y][Z] int32 (number of views that see the voxel).
- * workspace: NULL, or CNRMA_DENSE_WORKSPACE_BYTES of device memory zeroed once by the caller (one per call in flight).  It is
- *   only used by the lockstep schedules behind cnrma_debug_dense_tuning (monotonic arrival counters of their group
- *   barriers: never reset; a barrier that timed out or a change of the group size merely dephases later barriers -- a
- *   performance effect, never a correctness one).  The product schedule (free-running brick order) ignores it.
+ * workspace: NULL, or device memory owned by the caller, 8-byte aligned, one block per call in flight (calls on one stream may
+ *   share one).  Two parts:
+ *   - the first CNRMA_DENSE_WORKSPACE_BYTES, zeroed once by the caller: only used by the lockstep schedules behind
+ *     cnrma_debug_dense_tuning (monotonic arrival counters of their group barriers: never reset; a barrier that timed out or a
+ *     change of the group size merely dephases later barriers -- a performance effect, never a correctness one).
+ *   - behind them, CNRMA_DENSE_MASK_BYTES(X, Y, Z, V) for the view masks; no clearing needed.  When workspace_bytes >=
+ *     CNRMA_DENSE_WORKSPACE_BYTES + CNRMA_DENSE_MASK_BYTES(X, Y, Z, V) and the channels take more than one sweep of the kernel,
+ *     the first sweep is launched on its own and records, for every wave, one bit per view: does any of its 64 voxels project
+ *     into that view?  The other sweeps (a second launch on the same stream) walk the set bits only (a third of the (wave, view)
+ *     pairs at the north-star shape).  The bit is the first sweep's own test, made by the same code on the same lanes from the
+ *     same proj on every call (captured graphs included), so volume and count are bit-identical with and without the table.
+ *     With less room (NULL, the counters alone, one byte short) one launch walks all V views in every sweep.
+ *     cnrma_backproject_accum_h16 uses the workspace in the same way.
  * ---------------------------------------------------------------------------------------------------------- */
 #define CNRMA_DENSE_WORKSPACE_BYTES 1024
+/* room for the view masks: 8 bytes per wave (64 voxels) and 64 views, for the grid padded to whole bricks (at most 32^3 voxels
+ * = 512 waves each) and to a multiple of 8 bricks.  An over-estimate for the shipped 16 x 16 x 32 bricks. */
+#define CNRMA_DENSE_MASK_BYTES(X, Y, Z, V)                                                                              \
+  ((((((int64_t)(X) + 31) / 32) * (((int64_t)(Y) + 31) / 32) * (((int64_t)(Z) + 31) / 32) + 7) * 512) *               \
+   (((int64_t)(V) + 63) / 64) * 8)
 int cnrma_backproject_accum_f32(const float* feat_nhwc, const float* proj, int V, int C, int H, int W,
                                 int X, int Y, int Z, float voxel_size, float ox, float oy, float oz,
                                 float* volume, int32_t* count, void* workspace, int64_t workspace_bytes, void* stream);
