@@ -130,6 +130,12 @@ SIGNATURES = {
     "cnrma_fcaf3d_scores_f32": (c_int, [P, P, L, I, P, P, P]),
     "cnrma_nms_classes_workspace_bytes": (c_size_t, [I, I]),
     "cnrma_nms_classes_f32": (c_int, [P, I, P, I, I, P, I, P, F, F, P, c_size_t, P, P, P, I, P, P]),
+    "cnrma_fcaf3d_assign_workspace_bytes": (c_size_t, [L, I, I]),
+    "cnrma_fcaf3d_assign_f32": (c_int, [P, P, I, P, P, P, P, P, I, I, P, I, I, P, c_size_t, P, P, P, P, P, P]),
+    "cnrma_fcaf3d_focal_loss_workspace_bytes": (c_size_t, [L, I]),
+    "cnrma_fcaf3d_focal_loss_f32": (c_int, [P, P, P, I, P, I, F, F, P, c_size_t, P, P, P]),
+    "cnrma_fcaf3d_positive_losses_workspace_bytes": (c_size_t, [I]),
+    "cnrma_fcaf3d_positive_losses_f32": (c_int, [P, P, I, I, P, I, P, P, P, I, P, c_size_t, P, P, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -16,6 +16,7 @@ fcaf3d_head.py:64-98,107-139,275-298.
 A CoordSet owns the int32 coordinates [N,4] = (batch,x,y,z) of one lattice level, its hash map and the cached
 neighbour tables / strided children (what ME's CoordinateManager caches); a SparseTensor is (CoordSet, features).
 """
+import ctypes
 import itertools
 
 import os
@@ -1667,3 +1668,153 @@ def class_scores(cls_score, centerness):
         call("cnrma_fcaf3d_scores_f32", ptr(cls_score.contiguous().float()), ptr(centerness.contiguous().float()), n, nc,
              ptr(scores), ptr(mx), stream())
     return scores, mx
+
+
+# ---- training targets and detection losses on the device (include/cnrma.h a13) ---------------------------------------------
+class DeviceGT:
+    """Ground truth of one scene in fixed buffers on the device, for FCAF3DHead(device_targets=True): boxes [m_cap, 7] =
+    (gravity centre, dx, dy, dz, yaw), labels int64 [m_cap], n_live int32 [1] = how many of them are boxes.  The rows behind
+    n_live are never read.  A captured loss is replayed on other ground truth by copying into these three tensors."""
+
+    def __init__(self, boxes, labels, n_live):
+        assert boxes.dim() == 2 and boxes.shape[1] == 7 and labels.shape == (boxes.shape[0],) and n_live.numel() == 1
+        assert labels.dtype in (torch.int32, torch.int64) and n_live.dtype == torch.int32 and boxes.shape[0] >= 1
+        self.boxes, self.labels, self.n_live = boxes.float().contiguous(), labels.contiguous(), n_live
+
+    @staticmethod
+    def capacity(m):
+        """next multiple of 16 >= m, at least 16"""
+        return max(16, (int(m) + 15) // 16 * 16)
+
+    @classmethod
+    def from_boxes(cls, gt_bboxes, gt_labels, device, m_cap=None):
+        """pad (gravity centre, size, yaw) of a GTBoxes-like object and its labels to m_cap rows (default: capacity(m))"""
+        box = torch.cat((gt_bboxes.gravity_center, gt_bboxes.tensor[:, 3:]), dim=1).to(device).float()
+        m = box.shape[0]
+        m_cap = cls.capacity(m) if m_cap is None else int(m_cap)
+        assert m <= m_cap
+        boxes = torch.zeros((m_cap, 7), dtype=torch.float32, device=device)
+        labels = torch.zeros(m_cap, dtype=torch.int64, device=device)
+        if m:
+            boxes[:m] = box
+            labels[:m] = torch.as_tensor(gt_labels).to(device).long()
+        return cls(boxes, labels, torch.full((1,), m, dtype=torch.int32, device=device))
+
+
+def _level_array(level_cap):
+    caps = [int(c) for c in level_cap]
+    if not 1 <= len(caps) <= 8:
+        raise ValueError(f"1 to 8 levels, got {len(caps)}")
+    return caps, (ctypes.c_int32 * len(caps))(*caps)
+
+
+def assign_targets(points, level_cap, gt, limit, topk, level_live=None, cs=None):
+    """FCAF3DAssigner.assign on the device, without a host read.  points [n_cap, 3] = the levels concatenated, level_cap =
+    rows per level (host ints), level_live = device int32 [L] live rows per level (None: all), gt = DeviceGT.
+    Returns (labels int32 [n_cap], pos_row, pos_box int32 [P], pos_ctr float [P], n_pos int32 [1]) with P = m_cap * topk: the
+    positive rows in ascending row order; the rows behind n_pos hold row 0 / box 0 / target 0.
+    cs [m_cap, 2] = (cos(-yaw), sin(-yaw)) when the caller has them (a bit-for-bit comparison against the CPU wants the CPU's);
+    by default they are computed here, on the device."""
+    _lib.require_gpu()
+    points = points.detach().float().contiguous()
+    dev = points.device
+    caps, host_caps = _level_array(level_cap)
+    n_cap, m_cap = sum(caps), gt.boxes.shape[0]
+    if points.shape != (n_cap, 3):
+        raise ValueError(f"points {tuple(points.shape)} against level sizes {caps}")
+    if level_live is not None:
+        assert level_live.dtype == torch.int32 and level_live.numel() == len(caps)
+    boxes = gt.boxes
+    if cs is None:
+        yaw = -boxes[:, 6]
+        cs = torch.stack((torch.cos(yaw), torch.sin(yaw)), dim=1)
+    cs = cs.float().contiguous()
+    assert cs.shape == (m_cap, 2) and cs.device == dev
+    volume = (boxes[:, 3] * boxes[:, 4] * boxes[:, 5]).contiguous()
+    p_cap = m_cap * int(topk)
+    labels = torch.empty(n_cap, dtype=torch.int32, device=dev)
+    pos_row = torch.empty(p_cap, dtype=torch.int32, device=dev)
+    pos_box = torch.empty(p_cap, dtype=torch.int32, device=dev)
+    pos_ctr = torch.empty(p_cap, dtype=torch.float32, device=dev)
+    n_pos = torch.empty(1, dtype=torch.int32, device=dev)
+    nbytes = _lib.load().cnrma_fcaf3d_assign_workspace_bytes(n_cap, len(caps), m_cap)
+    if nbytes == 0:
+        raise ValueError(f"assign_targets: unsupported sizes (n_cap {n_cap}, {len(caps)} levels, m_cap {m_cap} of at most 1024)")
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    call("cnrma_fcaf3d_assign_f32", ptr(points), ctypes.addressof(host_caps), len(caps), ptr(level_live), ptr(boxes), ptr(cs),
+         ptr(volume), ptr(gt.labels), int(gt.labels.dtype == torch.int64), m_cap, ptr(gt.n_live), int(limit), int(topk),
+         ptr(ws), nbytes, ptr(labels), ptr(pos_row), ptr(pos_box), ptr(pos_ctr), ptr(n_pos), stream())
+    return labels, pos_row, pos_box, pos_ctr, n_pos
+
+
+class _FocalLossSum(torch.autograd.Function):
+    """un-normalised sigmoid focal loss over the live rows (one kernel + its fixed-order sum); backward = the stored
+    derivative times the incoming scalar"""
+
+    @staticmethod
+    def forward(ctx, cls_score, labels, caps, level_live, gamma, alpha):
+        x = cls_score.detach().float().contiguous()
+        n_cap, n_cls = x.shape
+        _, host_caps = _level_array(caps)
+        out = torch.empty((), dtype=torch.float32, device=x.device)
+        grad = torch.empty_like(x)
+        nbytes = _lib.load().cnrma_fcaf3d_focal_loss_workspace_bytes(n_cap, n_cls)
+        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=x.device)
+        call("cnrma_fcaf3d_focal_loss_f32", ptr(x), ptr(labels), ctypes.addressof(host_caps), len(caps), ptr(level_live), n_cls,
+             float(gamma), float(alpha), ptr(ws), nbytes, ptr(out), ptr(grad), stream())
+        ctx.save_for_backward(grad)
+        ctx.dtype = cls_score.dtype
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        (grad,) = ctx.saved_tensors
+        return (grad * g).to(ctx.dtype), None, None, None, None, None
+
+
+def focal_loss_sum(cls_score, labels, level_cap, level_live=None, gamma=2.0, alpha=0.25):
+    """sum over live rows and classes of the sigmoid focal loss (mmdet FocalLoss, use_sigmoid=True, before the division by
+    avg_factor); labels int32 [n_cap], anything outside [0, n_cls) = background.  Differentiable in cls_score."""
+    _lib.require_gpu()
+    caps = tuple(int(c) for c in level_cap)
+    if cls_score.dim() != 2 or cls_score.shape[0] != sum(caps) or labels.shape != (sum(caps),) or labels.dtype != torch.int32:
+        raise ValueError("focal_loss_sum: cls_score [n_cap, n_cls], labels int32 [n_cap], level sizes adding up to n_cap")
+    return _FocalLossSum.apply(cls_score, labels.contiguous(), caps, level_live, float(gamma), float(alpha))
+
+
+class _PositiveLossSums(torch.autograd.Function):
+    """centerness BCE and IoU3D loss over the positive rows (one kernel + its fixed-order sums); backward = the stored
+    derivatives times the incoming scalars"""
+
+    @staticmethod
+    def forward(ctx, logit, pred_boxes, gt_boxes, pos_box, pos_ctr, n_pos, rotated):
+        x = logit.detach().float().contiguous().view(-1)
+        b = pred_boxes.detach().float().contiguous()
+        p_cap, cols = b.shape
+        sums = torch.empty(3, dtype=torch.float32, device=x.device)
+        g_logit, g_box = torch.empty_like(x), torch.empty_like(b)
+        nbytes = _lib.load().cnrma_fcaf3d_positive_losses_workspace_bytes(p_cap)
+        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        call("cnrma_fcaf3d_positive_losses_f32", ptr(x), ptr(b), cols, int(bool(rotated)), ptr(gt_boxes), gt_boxes.shape[0],
+             ptr(pos_box), ptr(pos_ctr), ptr(n_pos), p_cap, ptr(ws), nbytes, ptr(sums), ptr(g_logit), ptr(g_box), stream())
+        ctx.save_for_backward(g_logit, g_box)
+        ctx.logit_shape, ctx.dtypes = logit.shape, (logit.dtype, pred_boxes.dtype)
+        return sums
+
+    @staticmethod
+    def backward(ctx, g):
+        g_logit, g_box = ctx.saved_tensors
+        return ((g_logit * g[0]).view(ctx.logit_shape).to(ctx.dtypes[0]), (g_box * g[1]).to(ctx.dtypes[1]),
+                None, None, None, None, None)
+
+
+def positive_loss_sums(logit, pred_boxes, gt, pos_box, pos_ctr, n_pos, rotated=False):
+    """over the P rows of assign_targets (n_pos live): float [3] = (sum BCE-with-logits(logit, pos_ctr), sum (1 - IoU3D(pred_boxes,
+    gt.boxes[pos_box])) * pos_ctr, sum pos_ctr), un-normalised.  logit [P] or [P, 1] = centerness[pos_row], pred_boxes [P, 6|7]
+    = the decoded boxes of those rows; rotated: IoU of boxes rotated about z (7 columns), else axis-aligned on the first six.
+    Differentiable in logit and pred_boxes."""
+    _lib.require_gpu()
+    p_cap = pos_box.shape[0]
+    if pred_boxes.shape[0] != p_cap or pred_boxes.shape[1] not in (6, 7) or logit.numel() != p_cap or (rotated and pred_boxes.shape[1] != 7):
+        raise ValueError(f"positive_loss_sums: {p_cap} rows, logit {tuple(logit.shape)}, boxes {tuple(pred_boxes.shape)}")
+    return _PositiveLossSums.apply(logit, pred_boxes, gt.boxes, pos_box.contiguous(), pos_ctr.contiguous(), n_pos, bool(rotated))

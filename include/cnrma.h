@@ -26,7 +26,7 @@ extern "C" {
 #endif
 
 #define CNRMA_EINVAL (-22)
-#define CNRMA_ABI_VERSION 7   /* 7: + the 16-bit feature-map entry points cnrma_backproject_accum_h16, cnrma_rma_neus_emit_rows_h16, cnrma_rma_emit_features_h16, cnrma_nchw_to_nhwc_b16; no signature changed; 6: the cnrma_debug_* entry points (and the experimental kernels behind them) left the product library: they exist in libcnrma_hip_exp.so (-DCNRMA_EXPERIMENTS) only; no signature changed; 5: + cnrma_sparse_conv_prepare_weights_bf16_t, cnrma_sparse_conv_wgrad_go_bf16, cnrma_sparse_conv_go_bf16 (+ its weight images), cnrma_bn_train_forward_f32 / _backward_f32; 4: gather-once convolution family, records-based point selection (SampleWs layout), *_ref_f32 hand-off */
+#define CNRMA_ABI_VERSION 7   /* the a13 target / loss entry points (cnrma_fcaf3d_assign_f32, _focal_loss_f32, _positive_losses_f32 and their workspace sizes) are additions inside version 7; 7: + the 16-bit feature-map entry points cnrma_backproject_accum_h16, cnrma_rma_neus_emit_rows_h16, cnrma_rma_emit_features_h16, cnrma_nchw_to_nhwc_b16; no signature changed; 6: the cnrma_debug_* entry points (and the experimental kernels behind them) left the product library: they exist in libcnrma_hip_exp.so (-DCNRMA_EXPERIMENTS) only; no signature changed; 5: + cnrma_sparse_conv_prepare_weights_bf16_t, cnrma_sparse_conv_wgrad_go_bf16, cnrma_sparse_conv_go_bf16 (+ its weight images), cnrma_bn_train_forward_f32 / _backward_f32; 4: gather-once convolution family, records-based point selection (SampleWs layout), *_ref_f32 hand-off */
 
 int cnrma_abi_version(void);
 
@@ -765,6 +765,59 @@ int cnrma_nms_classes_f32(const float* boxes, int box_cols, const float* scores,
                           int n_segments, const int32_t* valid, float score_thr, float iou_thr, void* workspace,
                           size_t workspace_bytes, float* out_boxes, float* out_scores, int64_t* out_labels, int out_cap,
                           int32_t* n_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * a13  training targets and detection losses on the device   replaces FCAF3DAssigner.assign / compute_centerness
+ *      (fcaf3d_head.py:395-484) and the loss body of FCAF3DHead._loss_single (:172-214: focal loss over all rows, centerness
+ *      BCE and IoU3D loss over the positive rows).  No [n, m] plane, no one-hot tensor, no device->host read: each entry point
+ *      is a linear chain of launches on `stream`, capturable in a graph, and bit-identical replay to replay.
+ * Rows: the levels concatenated -- level_cap[n_levels] (HOST array, n_levels <= 8, sum = n_cap) rows per level, of which the
+ *   first level_live[l] are live (DEVICE int32 [n_levels]; NULL = every row is live).  Dead rows may hold anything (NaN
+ *   included) and are never read.
+ *
+ * cnrma_fcaf3d_assign_f32: points [n_cap][3]; boxes [m_cap][7] = (gravity centre, dx, dy, dz, yaw), cs [m_cap][2] =
+ *   (cos(-yaw), sin(-yaw)), volume [m_cap], gt_label [m_cap] (int32, or int64 with label_is_i64 = 1), of which the first
+ *   m_live[0] (DEVICE word, 0 is legal) are live; 1 <= m_cap <= 1024.  Semantics of FCAF3DAssigner.assign operation for
+ *   operation in fp32: inside the box; on the box's best level (first level with fewer than `limit` inside points, minus one,
+ *   clamped at 0; the last level if none has fewer); centerness strictly greater than the min(topk + 1, n)-th largest of the
+ *   box's column (non-candidates count as -1; a radix select on the float bits, value-exact); then the smallest volume below
+ *   1e8, ties to the lowest box index.
+ *   Output: labels int32 [n_cap] (-1 on background and dead rows), and the positive rows in ascending row order:
+ *   pos_row / pos_box int32 [P_cap], pos_ctr float [P_cap] (the centerness target), n_pos[0] (DEVICE word), with
+ *   P_cap = m_cap * topk -- a bound, not a heuristic: condition 3 keeps at most topk rows per box and a row has one box.
+ *   Rows of pos_* behind n_pos hold row 0 / box 0 / target 0, so that fixed-shape gathers on them are harmless.
+ *   workspace: cnrma_fcaf3d_assign_workspace_bytes(n_cap, n_levels, m_cap) bytes, 16-byte aligned (0 = rejected arguments).
+ *
+ * cnrma_fcaf3d_focal_loss_f32: cls [n_cap][n_cls] logits, labels int32 [n_cap] (outside [0, n_cls) = background row) ->
+ *   loss_sum[0] = the un-normalised sum over live rows and classes of a_t (1 - p_t)^gamma BCE (mmdet FocalLoss,
+ *   use_sigmoid=True) and grad_cls [n_cap][n_cls], its derivative (zeros on dead rows).  Partial sums are combined in one
+ *   fixed order in fp64.  workspace: cnrma_fcaf3d_focal_loss_workspace_bytes(n_cap, n_cls) bytes, 8-byte aligned.
+ *
+ * cnrma_fcaf3d_positive_losses_f32: over the p_cap rows of the assignment, of which n_pos[0] are live: logit [p_cap] =
+ *   centerness[pos_row], pred_boxes [p_cap][box_cols] = the decoded boxes (cx, cy, cz, dx, dy, dz[, yaw]) of those rows,
+ *   boxes [m_cap][7] / pos_box / pos_ctr as above.  sums[0] = sum of BCE-with-logits(logit, pos_ctr), sums[1] = sum of
+ *   (1 - IoU3D(pred, boxes[pos_box])) * pos_ctr, sums[2] = sum of pos_ctr; grad_logit [p_cap] and grad_boxes
+ *   [p_cap][box_cols] are the derivatives of sums[0] / sums[1] (zeros on dead rows).  rotated = 0: axis-aligned IoU of the
+ *   first six columns (box_cols 6 or 7); rotated = 1 (box_cols 7): both boxes rotated about z, the geometry of
+ *   core/rotated_iou.py (16 edge crossings + 8 contained corners in angular order, shoelace) with the seven partial
+ *   derivatives carried through as forward-mode duals.
+ *   workspace: cnrma_fcaf3d_positive_losses_workspace_bytes(p_cap) bytes, 8-byte aligned.
+ * ---------------------------------------------------------------------------------------------------------- */
+size_t cnrma_fcaf3d_assign_workspace_bytes(int64_t n_cap, int n_levels, int m_cap);
+int cnrma_fcaf3d_assign_f32(const float* points, const int32_t* level_cap, int n_levels, const int32_t* level_live,
+                            const float* boxes, const float* cs, const float* volume, const void* gt_label,
+                            int label_is_i64, int m_cap, const int32_t* m_live, int limit, int topk, void* workspace,
+                            size_t workspace_bytes, int32_t* labels, int32_t* pos_row, int32_t* pos_box, float* pos_ctr,
+                            int32_t* n_pos, void* stream);
+size_t cnrma_fcaf3d_focal_loss_workspace_bytes(int64_t n_cap, int n_cls);
+int cnrma_fcaf3d_focal_loss_f32(const float* cls, const int32_t* labels, const int32_t* level_cap, int n_levels,
+                                const int32_t* level_live, int n_cls, float gamma, float alpha, void* workspace,
+                                size_t workspace_bytes, float* loss_sum, float* grad_cls, void* stream);
+size_t cnrma_fcaf3d_positive_losses_workspace_bytes(int p_cap);
+int cnrma_fcaf3d_positive_losses_f32(const float* logit, const float* pred_boxes, int box_cols, int rotated,
+                                     const float* boxes, int m_cap, const int32_t* pos_box, const float* pos_ctr,
+                                     const int32_t* n_pos, int p_cap, void* workspace, size_t workspace_bytes, float* sums,
+                                     float* grad_logit, float* grad_boxes, void* stream);
 
 #ifdef __cplusplus
 }

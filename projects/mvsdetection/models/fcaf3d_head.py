@@ -110,9 +110,10 @@ class FCAF3DHead(nn.Module):
                  loss_centerness=dict(type="CrossEntropyLoss", use_sigmoid=True, loss_weight=1.0),
                  loss_bbox=dict(type="IoU3DLoss", loss_weight=1.0),
                  loss_cls=dict(type="FocalLoss", use_sigmoid=True, gamma=2.0, alpha=0.25, loss_weight=1.0),
-                 train_cfg=None, test_cfg=None):
+                 train_cfg=None, test_cfg=None, device_targets=False):
         super().__init__()
         self.fp16_enabled = False
+        self.device_targets = bool(device_targets)      # True: targets and losses by the HIP kernels, no host read under loss()
         self.voxel_size = voxel_size
         self.yaw_parametrization = yaw_parametrization
         self.assigner = build_assigner(assigner) if assigner is not None else None
@@ -447,6 +448,8 @@ class FCAF3DHead(nn.Module):
         normalisers over the ranks)"""
         if self.assigner is None:
             raise ValueError("FCAF3DHead.loss needs an assigner (config key `assigner`)")
+        if self.device_targets:
+            return self._loss_single_device(centernesses, bbox_preds, cls_scores, points, gt_bboxes, gt_labels)
         if not hasattr(gt_bboxes, "gravity_center"):
             gt_bboxes = GTBoxes(torch.as_tensor(gt_bboxes))
         with torch.no_grad():
@@ -465,6 +468,46 @@ class FCAF3DHead(nn.Module):
         else:
             loss_centerness, loss_bbox = pos_ctr.sum(), pos_box.sum()
         return loss_centerness, loss_bbox, loss_cls
+
+
+    def _loss_single_device(self, centernesses, bbox_preds, cls_scores, points, gt_bboxes, gt_labels):
+        """_loss_single with the assignment and the three losses on the device (cnrma_amd.sparse.assign_targets /
+        focal_loss_sum / positive_loss_sums): fixed shapes -- the ground truth padded to a multiple of 16 boxes, the positive
+        rows in a block of m_cap * topk -- and device words for every count, so nothing is read back and the whole of it can be
+        captured in a graph.  gt_bboxes may be a sparse.DeviceGT (already padded; gt_labels is then ignored).  No boxes at all
+        is legal: loss_centerness = loss_bbox = 0 and the focal loss runs over all-background rows."""
+        a = self.assigner
+        if len(points) > a.n_scales:
+            raise ValueError(f"{len(points)} levels for an assigner with n_scales={a.n_scales}")
+        caps = [p.shape[0] for p in points] + [0] * (a.n_scales - len(points))     # a missing level holds no point
+        centerness, bbox_pred, cls_score, pts = map(torch.cat, (centernesses, bbox_preds, cls_scores, points))
+        dev = centerness.device
+        if isinstance(gt_bboxes, S.DeviceGT):
+            gt = gt_bboxes
+        else:
+            if not hasattr(gt_bboxes, "gravity_center"):
+                gt_bboxes = GTBoxes(torch.as_tensor(gt_bboxes))
+            gt = S.DeviceGT.from_boxes(gt_bboxes, gt_labels, dev)
+        with torch.no_grad():
+            labels, pos_row, pos_box, pos_ctr, n_pos = S.assign_targets(pts, caps, gt, a.limit, a.topk)
+        focal = S.focal_loss_sum(cls_score, labels, caps, None, self.loss_cls.gamma, self.loss_cls.alpha)
+        rows = pos_row.long()
+        boxes = self._bbox_pred_to_bbox(pts.index_select(0, rows), bbox_pred.index_select(0, rows))
+        rotated = bool(getattr(self.loss_bbox, "with_yaw", False)) and boxes.shape[1] >= 7
+        sums = S.positive_loss_sums(centerness.index_select(0, rows), boxes, gt, pos_box, pos_ctr, n_pos, rotated)
+        norm = _reduce_mean_device(torch.stack((n_pos[0].float(), sums[2].detach())))
+        n_norm, ctr_norm = norm[0].clamp(min=1.0), norm[1].clamp(min=1e-6)
+        return (self.loss_centerness.loss_weight * sums[0] / n_norm, self.loss_bbox.loss_weight * sums[1] / ctr_norm,
+                self.loss_cls.loss_weight * focal / n_norm)
+
+
+def _reduce_mean_device(t):
+    """_reduce_mean that stays on the device: the normalisers averaged over the ranks as one tensor"""
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        t = t.clone()
+        dist.all_reduce(t.div_(dist.get_world_size()))
+    return t
 
 
 def _reduce_mean(t):

@@ -1,4 +1,6 @@
-"""time of one training step of the detector at the ScanNet shape (features and TSDF given; detection losses only)"""
+"""time of one training step of the detector at the ScanNet shape (features and TSDF given; detection losses only)
+CNRMA_DEVICE_TARGETS=1: the head assigns its targets and computes its losses on the device (FCAF3DHead(device_targets=True));
+CNRMA_COUNT_READS=1: additionally one step under torch's sync debug mode, counting the device->host reads it warns about"""
 import os, sys, time, runpy
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
@@ -15,6 +17,8 @@ m = dict(cfg["model"])
 m.update(backbone2d=None, feature_2d=None, backbone_3d=None, tsdf_head=None)
 m.update(save_path="/tmp/cnrma_train_probe", voxel_dim_test=list(sc["dims"]), voxel_dim_train=list(sc["dims"]),
          use_feature_transform=False, point_sampler=os.environ.get("CNRMA_SAMPLER", "device"), detection_backbone=dict(type="FCAF3DBackbone", in_channels=C, depth=34))
+DEVICE_TARGETS = os.environ.get("CNRMA_DEVICE_TARGETS", "0") == "1"
+m["detection_head"] = dict(m["detection_head"], device_targets=DEVICE_TARGETS)
 torch.manual_seed(0)
 model = build_model(m)
 model.detection_backbone.init_weights(); model.detection_head.init_weights()
@@ -59,4 +63,13 @@ if os.environ.get("CNRMA_CPROFILE"):
     torch.cuda.synchronize(); pr.disable()
     st = pstats.Stats(pr); st.sort_stats("tottime").print_stats(28)
     st.sort_stats("cumulative").print_stats(110)
-print(f"{shape} ({'bf16 autocast' if AUTOCAST else 'fp32'}): {(time.perf_counter() - t0) / n * 1e3:.1f} ms per training step, loss {l:.4f}, peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
+if os.environ.get("CNRMA_COUNT_READS"):
+    import warnings
+    torch.cuda.set_sync_debug_mode("warn")
+    with warnings.catch_warnings(record=True) as seen:
+        warnings.simplefilter("always")
+        step()
+    torch.cuda.set_sync_debug_mode("default")
+    print(f"device->host reads in one step (synchronizing calls torch warns about; the step's own float(loss) is one of them): "
+          f"{sum('synchroniz' in str(w.message) for w in seen)}")
+print(f"{shape} ({'bf16 autocast' if AUTOCAST else 'fp32'}, targets and losses {'on the device' if DEVICE_TARGETS else 'in torch'}): {(time.perf_counter() - t0) / n * 1e3:.1f} ms per training step, loss {l:.4f}, peak memory {torch.cuda.max_memory_allocated() / 2**30:.1f} GiB")
