@@ -157,6 +157,54 @@ def elu(x):
     return np.where(x > 0, x, np.expm1(np.minimum(x, 0)))
 
 
+def max_pool_backward(coords, feats, grad_out, tensor_stride):
+    """gradient of max_pool() w.r.t. feats (fp64): every input row has one parent; it receives the parent's gradient in the
+    channels where it attains the parent's maximum (distinct values per window and channel: exactly one child does)"""
+    coords = np.asarray(coords, dtype=np.int64)
+    out_coords, out = max_pool(coords, feats, tensor_stride)
+    look = Lookup(coords)
+    F, G = np.asarray(feats, dtype=np.float64), np.asarray(grad_out, dtype=np.float64)
+    gF = np.zeros_like(F)
+    for off in kernel_offsets(2, tensor_stride):
+        q = out_coords.copy()
+        q[:, 1:] += off
+        idx = look(q)
+        m = idx >= 0
+        gF[idx[m]] = G[m] * (F[idx[m]] == out[m])
+    return gF
+
+
+def _act_slope(v, act):
+    """d act(v) / dv of the pre-activation v: act None / "relu" / "elu" (alpha 1)"""
+    if act == "relu":
+        return (v > 0).astype(np.float64)
+    return np.where(v > 0, 1.0, np.exp(np.minimum(v, 0))) if act == "elu" else np.ones_like(v)
+
+
+def batch_norm_train(x, w, b, eps, residual=None, act=None):
+    """nn.BatchNorm1d in training mode over the rows of x [n, C], + residual, + activation, in fp64 ->
+    (y, {mean, var (biased), xhat, pre (the activation's argument)})"""
+    x, w, b = (np.asarray(a, dtype=np.float64) for a in (x, w, b))
+    mean = x.mean(0)
+    var = ((x - mean) ** 2).mean(0)
+    xhat = (x - mean) / np.sqrt(var + eps)
+    pre = xhat * w + b
+    if residual is not None:
+        pre = pre + np.asarray(residual, dtype=np.float64)
+    y = relu(pre) if act == "relu" else (elu(pre) if act == "elu" else pre)
+    return y, dict(mean=mean, var=var, xhat=xhat, pre=pre)
+
+
+def batch_norm_train_backward(x, w, b, eps, grad_out, residual=None, act=None):
+    """gradients of sum(batch_norm_train(...) * grad_out) -> (dx, dresidual or None, dw, db), fp64"""
+    _, st = batch_norm_train(x, w, b, eps, residual, act)
+    g = np.asarray(grad_out, dtype=np.float64) * _act_slope(st["pre"], act)
+    xhat = st["xhat"]
+    dw, db = (g * xhat).sum(0), g.sum(0)
+    dx = np.asarray(w, dtype=np.float64) / np.sqrt(st["var"] + eps) * (g - g.mean(0) - xhat * (g * xhat).mean(0))
+    return dx, (g if residual is not None else None), dw, db
+
+
 def union_add(ca, fa, cb, fb):
     """A rows first (in order), then the B-only rows (in order); features summed where both exist."""
     ca, cb = np.asarray(ca, dtype=np.int64), np.asarray(cb, dtype=np.int64)

@@ -128,6 +128,47 @@ def edge_facts(g):
 
 
 # ---------------------------------------------------------------------------------------------------------------------
+# BatchNorm + activation inputs whose pre-activation stays clear of the ReLU / ELU kink (tests/test_sparse_backward_edges_gpu.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def clear_of_kink(x, w, b, eps, residual, act, margin=0.05):
+    """fp32 (x, b, residual) whose fp64 pre-activation bn(x) * w + b [+ residual] has no element within `margin` of 0, so that an
+    fp32 kernel and the fp64 reference take the same branch of the activation at EVERY element (nothing is masked out of a
+    comparison).  With a residual the close elements of the residual move; without one a single bias per column cannot clear
+    a thousand rows, so the close elements of x move (and the bias of a constant column, whose x cannot matter)."""
+    from oracle import sparse_oracle as SO
+    x, b = np.array(x), np.array(b, dtype=np.float32)          # x keeps its type where only the residual moves
+    residual = None if residual is None else np.array(residual, dtype=np.float32)
+    if act is None:
+        return x, b, residual
+    pre = SO.batch_norm_train(x, w, b, eps, residual, act)[1]["pre"]
+    if residual is not None:
+        near = np.abs(pre) < margin
+        residual[near] += np.where(pre >= 0, 2 * margin, -2 * margin)[near].astype(np.float32)
+    else:
+        x = x.astype(np.float32)
+        flat = x.astype(np.float64).var(0) == 0
+        b[flat & (np.abs(b) < 2 * margin)] = 3 * margin
+        if x.shape[0] <= 8:             # a few rows (two rows are always xhat = -1, +1): here a bias per column does clear them
+            xw = SO.batch_norm_train(x, w, 0 * b, eps, None, act)[1]["pre"]
+            cand = np.concatenate((b[None], np.repeat(np.linspace(-2, 2, 81, dtype=np.float32)[:, None], len(b), axis=1)))
+            gap = np.abs(xw[None] + cand[:, None, :]).min(axis=1)                   # [candidate, column]
+            gap[0] = np.where(gap[0] >= 2 * margin, np.inf, gap[0])                 # the bias given stays where it is clear already
+            b = np.where(flat, b, cand[gap.argmax(axis=0), np.arange(len(b))]).astype(np.float32)
+        for _ in range(100):
+            st = SO.batch_norm_train(x, w, b, eps, None, act)[1]
+            pre = st["pre"]
+            near = (np.abs(pre) < margin) & ~flat
+            if not near.any():
+                break
+            slope = np.asarray(w, dtype=np.float64) / np.sqrt(st["var"] + eps)
+            step = (np.where(pre >= 0, 1.6 * margin, -1.6 * margin) - pre) / slope
+            x[near] = (x.astype(np.float64) + step)[near].astype(np.float32)
+    pre = SO.batch_norm_train(x, w, b, eps, residual, act)[1]["pre"]
+    assert np.abs(pre).min() >= 0.8 * margin, np.abs(pre).min()
+    return x, b, residual
+
+
+# ---------------------------------------------------------------------------------------------------------------------
 # sparse tensors whose capacity exceeds their live row count (tests/test_sparse_edges_gpu.py)
 # ---------------------------------------------------------------------------------------------------------------------
 POISON = 3e38           # a dead feature / residual value: finite, safe to read, and 3e38 * anything visible in any sum or maximum

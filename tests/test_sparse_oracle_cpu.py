@@ -259,3 +259,61 @@ def test_weight_image_encodings_are_exact_and_padding_is_zero(kind):
     Wt = np.ascontiguousarray(W[::-1].transpose(0, 2, 1))
     assert np.array_equal(SO.weight_image(kind, W, transpose=True, flip=True), SO.weight_image(kind, Wt))
     assert not np.array_equal(SO.weight_image(kind, W, transpose=True, flip=False), SO.weight_image(kind, Wt))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the oracle's training-mode BatchNorm and max-pool gradients against central differences of their own fp64 forward
+# (what tests/test_sparse_backward_edges_gpu.py measures the HIP kernels against)
+# ---------------------------------------------------------------------------------------------------------------------
+def _central(f, a, h=1e-5):
+    """d f() / d a by central differences, a perturbed in place element by element"""
+    g = np.zeros_like(a)
+    for i in np.ndindex(*a.shape):
+        keep = a[i]
+        a[i] = keep + h
+        up = f()
+        a[i] = keep - h
+        g[i] = (up - f()) / (2 * h)
+        a[i] = keep
+    return g
+
+
+@pytest.mark.parametrize("act", [None, "relu", "elu"])
+@pytest.mark.parametrize("with_res", [False, True])
+@pytest.mark.parametrize("n,C", [(5, 4), (9, 8)])
+def test_batch_norm_train_backward_matches_finite_differences(n, C, with_res, act):
+    from helpers import clear_of_kink
+    rng = np.random.RandomState(100 * n + C)
+    eps = 1e-5
+    w = 0.5 + rng.rand(C)
+    x, b, r = clear_of_kink(rng.randn(n, C) * 2 + 1, w, rng.randn(C), eps, rng.randn(n, C) if with_res else None, act)
+    x, b, r = x.astype(np.float64), b.astype(np.float64), None if r is None else r.astype(np.float64)
+    G = rng.randn(n, C)
+    y, st = SO.batch_norm_train(x, w, b, eps, r, act)
+    assert act is None or np.abs(st["pre"]).min() > 0.04          # a step of 1e-5 crosses no kink
+    np.testing.assert_allclose(st["mean"], x.mean(0), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(st["var"], x.var(0), rtol=1e-12, atol=1e-12)
+    np.testing.assert_allclose(y, {None: lambda v: v, "relu": SO.relu, "elu": SO.elu}[act](st["pre"]), rtol=0, atol=0)
+    dx, dr, dw, db = SO.batch_norm_train_backward(x, w, b, eps, G, r, act)
+    loss = lambda: float((SO.batch_norm_train(x, w, b, eps, r, act)[0] * G).sum())
+    for got, arg in ((dx, x), (dw, w), (db, b)) + (((dr, r),) if with_res else ()):
+        fd = _central(loss, arg)
+        assert np.abs(got - fd).max() <= 1e-6 * np.abs(fd).max(), (np.abs(got - fd).max(), np.abs(fd).max())
+    assert (dr is None) == (not with_res)
+
+
+@pytest.mark.parametrize("n,C,ts", [(5, 4, 1), (9, 8, 2)])
+def test_max_pool_backward_matches_finite_differences(n, C, ts):
+    rng = np.random.RandomState(n)
+    xyz = np.stack(np.meshgrid(*[np.arange(-1, 2)] * 3, indexing="ij"), axis=-1).reshape(-1, 3)
+    c = np.concatenate((np.zeros((n, 1), dtype=np.int64), xyz[rng.permutation(27)[:n]] * ts), axis=1)
+    f = rng.randn(n, C)
+    oc, out = SO.max_pool(c, f, ts)
+    assert 1 < len(oc) < n                                         # windows with several children and more than one window
+    s = np.sort(f, axis=0)
+    assert (s[1:] - s[:-1]).min() > 1e-4                           # distinct values: a step of 1e-5 changes no argmax
+    G = rng.randn(*out.shape)
+    got = SO.max_pool_backward(c, f, G, ts)
+    fd = _central(lambda: float((SO.max_pool(c, f, ts)[1] * G).sum()), f)
+    assert np.abs(got - fd).max() <= 1e-6 * np.abs(fd).max()
+    assert (np.count_nonzero(got, axis=0) == len(oc)).all()        # one child per window and channel takes the gradient
