@@ -136,6 +136,9 @@ SIGNATURES = {
     "cnrma_fcaf3d_focal_loss_f32": (c_int, [P, P, P, I, P, I, F, F, P, c_size_t, P, P, P]),
     "cnrma_fcaf3d_positive_losses_workspace_bytes": (c_size_t, [I]),
     "cnrma_fcaf3d_positive_losses_f32": (c_int, [P, P, I, I, P, I, P, P, P, I, P, c_size_t, P, P, P, P]),
+    "cnrma_mesh_workspace_bytes": (c_size_t, [I, I, I]),
+    "cnrma_mesh_count_f32": (c_int, [P, I, I, I, P, c_size_t, P, P]),
+    "cnrma_mesh_emit_f32": (c_int, [P, I, I, I, F, P, P, P, P, L, P, L, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -819,6 +819,38 @@ int cnrma_fcaf3d_positive_losses_f32(const float* logit, const float* pred_boxes
                                      const int32_t* n_pos, int p_cap, void* workspace, size_t workspace_bytes, float* sums,
                                      float* grad_logit, float* grad_boxes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * a14  mesh of a TSDF volume: marching cubes on the device   replaces TSDF.get_mesh (datasets/tsdf.py:81-114: scikit-image on
+ *      the host).  Classic marching cubes with the case table of cnrma_amd/mesh_table.py (csrc/mesh_table.inc): ambiguous faces
+ *      are resolved from the face's own four signs, so neighbouring cells agree and the mesh has no cracks.  It is NOT
+ *      scikit-image's Lewiner variant triangle for triangle; the edge vertices are the same linear interpolation.
+ * tsdf [X][Y][Z] fp32 (z fastest), X*Y*Z <= 2^28.  Field: g = (v == 1) ? 1 : clamp(-v, -1, 1) (tsdf.py:81-114: unobserved
+ *   voxels count as inside, level 0); a corner is inside when g > 0 (0 and NaN are outside).  The mesh is EMPTY when no voxel has
+ *   g < 0 or none has g > 0 (tsdf.py:81-114: min >= 0 or max <= 0), and when an extent is below 2.
+ *
+ * cnrma_mesh_workspace_bytes (tsdf.py:81-114): host arithmetic; 0 for arguments the entry points reject.  About 9.1 bytes per
+ *   voxel: the compacted list is sized for the worst case, every voxel on it.
+ * cnrma_mesh_count_f32 (tsdf.py:81-114): three launches (classify, scan of the block totals, classify + compact) ->
+ *   counts[4] (DEVICE) = {n_vertices, n_triangles, n_active_cells, flags}, flags = CNRMA_MESH_HAS_NEGATIVE | CNRMA_MESH_HAS_POSITIVE
+ *   as found; the three numbers are 0 for an empty mesh.  workspace: 16-byte aligned, not cleared; it is the input of the emit.
+ * cnrma_mesh_emit_f32 (tsdf.py:81-114): one launch over the compacted list -> vertices / normals [v_cap][3] fp32, faces
+ *   [f_cap][3] int32.  A vertex is the sign change on an edge owned by its lower voxel: t = g0 / (g0 - g1), position = (voxel
+ *   index + t on the edge's axis) * voxel_size + origin3_dev[axis] (un-fused); normal = -(gradient of g interpolated with t between
+ *   the edge's ends; central differences * 0.5, one-sided at the border), divided by its length, (0, 0, 0) when that is 0.  Vertex
+ *   order: owner (x Y + y) Z + z, then axis; face order: cell index, then table order; faces are counter-clockwise seen from
+ *   outside (g <= 0).  Bit-identical from run to run.  Rows at or beyond v_cap / f_cap are never written: a caller whose
+ *   capacities are too small sees the true need in counts.  Neither entry point allocates, synchronises or reads the
+ *   environment.
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CNRMA_MESH_HAS_NEGATIVE 1
+#define CNRMA_MESH_HAS_POSITIVE 2
+size_t cnrma_mesh_workspace_bytes(int X, int Y, int Z);
+int cnrma_mesh_count_f32(const float* tsdf, int X, int Y, int Z, void* workspace, size_t workspace_bytes, int32_t* counts,
+                         void* stream);
+int cnrma_mesh_emit_f32(const float* tsdf, int X, int Y, int Z, float voxel_size, const float* origin3_dev,
+                        const void* workspace, float* vertices, float* normals, int64_t v_cap, int32_t* faces, int64_t f_cap,
+                        const int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,8 @@
 the lane id and never materialises it).  `TSDF` holds a truncated signed distance volume with the metadata needed to
 interpret it -- npz I/O in the reference's file format, device moves, and the resampling under a rigid transform that the
 space-transform pipelines use (:112-180).  Mesh extraction needs scikit-image + trimesh (third-party, absent in this
-image): get_mesh() raises ImportError without them and the detectors then skip the .ply export only."""
+image): get_mesh() raises ImportError without them and the detectors then skip the .ply export only.  get_mesh_device() is the
+library's own marching cubes on the GPU (cnrma_amd.mesh), which needs neither."""
 import numpy as np
 import torch
 
@@ -51,6 +52,13 @@ class TSDF:
         mc = getattr(measure, "marching_cubes", None) or measure.marching_cubes_lewiner
         verts, faces, norms, _ = mc(vol, level=0)
         return trimesh.Trimesh(vertices=verts * self.voxel_size + self.origin.cpu().numpy(), faces=faces, vertex_normals=norms)
+
+    def get_mesh_device(self):
+        """the mesh from the library's marching cubes on the GPU (cnrma_amd.mesh.marching_cubes: the same field, level and
+        empty rule as get_mesh, classic case table instead of scikit-image's Lewiner variant); a cnrma_amd.mesh.Mesh with
+        .export(path).  Raises the library's CnrmaError when it is not built or the volume is not on a GPU."""
+        from cnrma_amd import mesh
+        return mesh.marching_cubes(self.tsdf_vol, self.voxel_size, self.origin)
 
     def transform(self, transform=None, voxel_dim=None, origin=None, align_corners=False):
         """resample under the rigid map `transform` (new world -> old world, 4x4 or 3x4) into a volume of `voxel_dim`

@@ -10,9 +10,10 @@ from .multiview_base import MultiViewBase
 class Atlas(MultiViewBase):
     def __init__(self, pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin,
                  backbone2d_stride, backbone2d, feature_2d, backbone_3d, tsdf_head, save_path, train_cfg=None,
-                 test_cfg=None, pretrained=None):
+                 test_cfg=None, pretrained=None, mesh_extractor=None):
         super().__init__(pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin,
-                         backbone2d_stride, backbone2d, feature_2d, backbone_3d, tsdf_head, save_path)
+                         backbone2d_stride, backbone2d, feature_2d, backbone_3d, tsdf_head, save_path,
+                         mesh_extractor=mesh_extractor)
         assert self.backbone3d is not None and self.tsdf_head is not None, "Atlas is the 3D reconstruction network"
         self.initialize_volume()
 

@@ -23,8 +23,13 @@ class MultiViewBase(nn.Module):
     channels_last_2d = True
 
     def __init__(self, pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin,
-                 backbone2d_stride, backbone2d, feature_2d, backbone_3d, tsdf_head, save_path):
+                 backbone2d_stride, backbone2d, feature_2d, backbone_3d, tsdf_head, save_path, mesh_extractor=None):
         super().__init__()
+        # who writes {scene}.ply: None = the reference's TSDF.get_mesh (scikit-image + trimesh; no .ply without them),
+        # "device" = the library's marching cubes on the GPU (TSDF.get_mesh_device)
+        if mesh_extractor not in (None, "device"):
+            raise ValueError(f"mesh_extractor must be None or 'device', got {mesh_extractor!r}")
+        self.mesh_extractor = mesh_extractor
         self.fp16_enabled = False
         # a sub-network given as None is not built: its OUTPUT then comes in as an input (`features`, `tsdf`) -- that
         # is how the hot path is measured, with the 2D / 3D CNN results resident in HBM
@@ -127,7 +132,8 @@ class MultiViewBase(nn.Module):
         return outs
 
     def save_reconstruction(self, outputs, inputs):
-        """{save_path}/{scene}/{scene}.npz for every sample, + {scene}.ply when scikit-image / trimesh are installed"""
+        """{save_path}/{scene}/{scene}.npz for every sample, + {scene}.ply when scikit-image / trimesh are installed or, with
+        mesh_extractor="device", from the library's own marching cubes"""
         if "offset" not in inputs or "scene" not in inputs:
             return []
         results = self.post_process(outputs, inputs)
@@ -135,6 +141,9 @@ class MultiViewBase(nn.Module):
             d = os.path.join(self.save_path, r["scene"])
             os.makedirs(d, exist_ok=True)
             r["scene_tsdf"].save(os.path.join(d, r["scene"] + ".npz"))
+            if self.mesh_extractor == "device":
+                r["scene_tsdf"].get_mesh_device().export(os.path.join(d, r["scene"] + ".ply"))
+                continue
             try:
                 r["scene_tsdf"].get_mesh().export(os.path.join(d, r["scene"] + ".ply"))
             except ImportError:

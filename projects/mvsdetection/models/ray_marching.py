@@ -60,9 +60,9 @@ class RayMarching(MultiViewBase):
                  train_cfg=None, test_cfg=None, pretrained=None, use_feature_transform=True,
                  ray_marching_type="neus", depth_points=None, neus_threshold=None, middle_save_path=None,
                  middle_visualize_path=None, point_sampler="device", static_test=True, static_slots=3, static_calibration=2,
-                 static_feature_handoff="reference", static_feature_dtype="float32", static_nms=None):
+                 static_feature_handoff="reference", static_feature_dtype="float32", static_nms=None, mesh_extractor=None):
         super().__init__(pixel_mean, pixel_std, voxel_size, n_scales, voxel_dim_train, voxel_dim_test, origin, backbone2d_stride,
-                         backbone2d, feature_2d, backbone_3d, tsdf_head, save_path)
+                         backbone2d, feature_2d, backbone_3d, tsdf_head, save_path, mesh_extractor=mesh_extractor)
         self.detection_backbone = build_backbone(detection_backbone)
         self.detection_head = build_head(detection_head)
         if not use_feature_transform:
