@@ -210,18 +210,32 @@ def check_nms_setting(nms):
     return None if nms is None else dict(nms)
 
 
+def _read_back(out, extra=()):
+    """the ONE device->host read of a static output, on the current stream once out["done"] has completed: the host values of
+    `valid`, `counts` and the `extra` words, in that order.  Raises when the pass violated an assumption of its plan (status != 0)."""
+    if out.get("done") is not None:
+        torch.cuda.current_stream(out["bboxes"].device).wait_event(out["done"])
+    host = _lib.read_ints(torch.cat([out[k].view(-1) for k in ("status", "valid", "counts", *extra)]))
+    if host[0] != 0:
+        raise _lib.CnrmaError(f"{host[0]} capacity / branch assumption(s) of the static plan violated: re-run eagerly")
+    return host[1:]
+
+
+def _live_rows(sizes, valid, device):
+    """index of the detections in a padded block: level l owns rows [sum(sizes[:l]), +sizes[l]), the first valid[l] are live"""
+    rows, r0 = [], 0
+    for k, v in zip(sizes, valid):
+        rows.append(torch.arange(r0, r0 + v, device=device))
+        r0 += k
+    return torch.cat(rows)
+
+
 def final_detections(out):
     """(boxes [K, 6|7], scores [K], labels [K]) of a static output traced with nms=...: what postprocess.nms makes of
     detections(out), after ONE device->host read (status, valid, counts and the detection count together)"""
     if "nms_n" not in out:
         raise _lib.CnrmaError("this static trace was built without nms=...: it ends at the raw detections")
-    if out.get("done") is not None:
-        torch.cuda.current_stream(out["bboxes"].device).wait_event(out["done"])
-    host = _lib.read_ints(torch.cat((out["status"].view(-1), out["valid"].view(-1), out["counts"].view(-1),
-                                     out["nms_n"].view(-1))))
-    if host[0] != 0:
-        raise _lib.CnrmaError(f"{host[0]} capacity / branch assumption(s) of the static plan violated: re-run eagerly")
-    k = min(host[-1], out["nms_boxes"].shape[0])
+    k = min(_read_back(out, ("nms_n",))[-1], out["nms_boxes"].shape[0])
     return out["nms_boxes"][:k], out["nms_scores"][:k], out["nms_labels"][:k]
 
 
@@ -259,7 +273,55 @@ def trace_net(plan, backbone, head, coords, feats, n_dev, voxel_size, device, ex
     return out
 
 
-class StaticNet:
+class _StaticGraph:
+    """What StaticNet, StaticScene and StaticBatch share: a launch sequence (`_trace`, run under the object's size plan) on the
+    object's own stream, traced once plainly and once under stream capture, then replayed per call on inputs that `_load`
+    staged into static buffers.  Subclasses bring `_load`, `_trace` and what is theirs alone."""
+
+    def __init__(self, device, margin, stream):
+        self.device = torch.device(device)
+        self.margin = margin
+        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
+        self.plan = self.graph = self.out = self.done = None
+
+    def _enter(self, *tensors):
+        """order self.stream behind the caller's stream (the 2D backbone / Atlas head that produced the inputs ran there) and
+        keep the inputs' memory from being recycled while self.stream still reads it"""
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self.stream:
+            self.stream.wait_stream(cur)
+            for t in tensors:
+                if torch.is_tensor(t) and t.is_cuda:
+                    t.record_stream(self.stream)
+
+    def _capture(self, capture):
+        """with the inputs loaded and self.stream current: the plain static run (it creates the trace's device constants and is
+        what the tests compare with the eager result), then the same sequence under stream capture"""
+        self.out = self._trace()
+        self.stream.synchronize()
+        if capture:
+            self._record()
+            self.stream.synchronize()
+
+    def _record(self, graph=None):
+        """the launch sequence under stream capture, into `graph` when a subclass brings its own"""
+        self.graph = graph if graph is not None else torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=self.stream):
+            self.out = self._trace()
+
+    def _replay(self):
+        """with the inputs loaded and self.stream current: one pass, and the event that tells its end"""
+        if self.graph is not None:
+            self.graph.replay()
+        else:
+            self.out = self._trace()
+        self.done = torch.cuda.Event()
+        self.done.record()
+        self.out["done"] = self.done
+        return self.out
+
+
+class StaticNet(_StaticGraph):
     """The sparse half alone (point rows -> raw detections) as a replayable HIP graph: what StaticScene runs after the
     aggregation, without the geometric half in front.  Used to pin the graph path of the network to the oracle on
     arbitrary point sets (tests) and by callers that bring their own points."""
@@ -267,12 +329,9 @@ class StaticNet:
     def __init__(self, backbone, head, voxel_size, device, margin=1.2, stream=None, nms=None):
         """nms: None (the trace ends at the raw detections) or dict(score_thr=..., iou_thr=...): the per-class NMS runs on the
         device at the end of the trace (out["nms_boxes" / "nms_scores" / "nms_labels" / "nms_n"], final_detections())"""
+        super().__init__(device, margin, stream)
         self.backbone, self.head, self.voxel_size = backbone, head, voxel_size
         self.nms, self._nms_state = check_nms_setting(nms), {}
-        self.device = torch.device(device)
-        self.margin = margin
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
-        self.plan = self.graph = self.out = None
 
     def build(self, coords, feats, capture=True, cap=None):
         """calibrate eagerly on (coords [M,3], feats [M,C]), then trace statically at point capacity `cap` (default M)
@@ -294,13 +353,7 @@ class StaticNet:
             self.feats = torch.zeros((self.cap, C), dtype=torch.float32, device=self.device)
             self.n_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
             self._load(coords, feats)
-            self.out = self._trace()
-            self.stream.synchronize()
-            if capture:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=self.stream):
-                    self.out = self._trace()
-                self.stream.synchronize()
+            self._capture(capture)
         return dict(bboxes=bboxes, scores=scores, level_rows=[len(l) for l in levels])
 
     def _load(self, coords, feats):
@@ -318,33 +371,16 @@ class StaticNet:
         self.plan.end_static()
         return out
 
-    def _enter(self, *inputs):
-        """order self.stream behind the caller's stream (which produced the inputs) and keep their memory from being recycled
-        while self.stream still reads it"""
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.stream:
-            self.stream.wait_stream(cur)
-            for t in inputs:
-                if torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(self.stream)
-
     def run(self, coords, feats):
         self._enter(coords, feats)
         with torch.cuda.stream(self.stream):
             self._load(coords, feats)
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self.out = self._trace()
-            self.done = torch.cuda.Event()
-            self.done.record()
-        self.out["done"] = self.done
-        return self.out
+            return self._replay()
 
     final_detections = staticmethod(final_detections)
 
 
-class StaticScene:
+class StaticScene(_StaticGraph):
     """One scene forward as a replayable HIP graph: the whole launch sequence of forward_scene() (dense unprojection,
     march, selection, voxelisation, MinkResNet34, neck/head, decode -- ~350 launches) captured once and replayed per
     scene with a single host call; no device->host read, no allocation, no Python in between.
@@ -374,16 +410,17 @@ class StaticScene:
                 raise ValueError(f"feature_dtype must be torch.float32, torch.float16 or torch.bfloat16, got {feature_dtype}")
             if cfg.ray_marching_type != "neus":
                 raise ValueError("16-bit feature maps are read by the NeuS path only: depth mode takes a float32 slot")
-        self.device = torch.device(device)
-        self.margin, self.dense = margin, dense
+        super().__init__(device, margin, stream)
+        self.dense = dense
         # feature hand-off of channels-last maps (run()'s `by_reference` overrides it per scene): True = the trace reads the
         # caller's tensor in place for the WHOLE replay; False = copied into the slot's own buffer first
         self.by_reference = bool(by_reference)
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
-        self.graph = None
-        self.plan = None
-        self.out = None
-        self._copied = None
+        self._copied = self._held = None
+        self.nhwc = self.march = self.march_out = self.seed_dev = None      # static input buffers: _alloc_inputs (build)
+        self._dense_ws = self._side = None     # the dense kernel's workspace and DENSE_BRANCH's stream, made on first use
+        self.n_nodes = None                # launches per scene of the captured graph (bench: graph_nodes_per_scene)
+        self.arena_fallbacks = 0
+        self.outgrown, self.n_outgrown = None, 0      # sizes of the scenes that outgrew the plan since the last (re)build
         self.check_weights = True          # compare the weights' fingerprint before every replay (~20 us of host time)
         self._weights = weight_tensors(backbone, head)
         self._tag = None
@@ -487,59 +524,56 @@ class StaticScene:
         self._consumed = torch.cuda.Event()      # copies and the layout pass are behind this point: unless the maps are read
         self._consumed.record()                  # by reference (self._held), the caller's feature tensor is free again
 
-    def _enter(self, *inputs):
-        """order self.stream behind the caller's stream (the 2D backbone / Atlas head that produced the inputs ran
-        there) and keep the inputs' memory from being recycled while self.stream still reads it"""
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.stream:
-            self.stream.wait_stream(cur)
-            for t in inputs:
-                if torch.is_tensor(t) and t.is_cuda:
-                    t.record_stream(self.stream)
-
     def _dense_workspace(self):
         """this scene's own workspace of the dense kernel (arrival counters + view masks): the captured graph replays into it, so
         it lives as long as the scene"""
-        if getattr(self, "_dense_ws", None) is None:
+        if self._dense_ws is None:
             self._dense_ws = rma.dense_workspace(self.device, self.cfg.dims, self.shape_nhwc[0], self.shape_nhwc[3],
                                                  self.feature_dtype in rma.ELEM_CODES)
         return self._dense_ws
 
     # ---- the launch sequence ---------------------------------------------------------------------------------------
+    def _geometry(self, seed=0x5EED, defer_feats=False, side=None):
+        """the geometric half of a static trace on the inputs this scene has loaded: the dense unprojection (self.dense; on the
+        stream `side` when given) and the aggregation with its point selection, drawn with cfg.sample_seed when that is fixed
+        (every replay draws the same subset, as forward_scene) and with `seed` + the scene's device counter otherwise.
+        Returns ((volume, count) or None, coords, feats, n_sel, info); stepping seed_dev is left to the caller's sequence."""
+        cfg = self.cfg
+        dense = None
+        if self.dense:
+            with torch.cuda.stream(side if side is not None else torch.cuda.current_stream(self.device)):
+                dense = rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin, cfg.stride,
+                                              proj_scaled=self.proj_scaled, feat_ref=self.feat_ref, shape=self.shape_nhwc,
+                                              feat_dtype=self.feature_dtype, workspace=self._dense_workspace())
+        fixed = cfg.sample_seed is not None
+        return (dense,) + rma.aggregate_points_static(
+            self.nhwc, self.proj_inv, self.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
+            max_points=cfg.max_points, seed=cfg.sample_seed if fixed else seed, seed_dev=None if fixed else self.seed_dev,
+            marched=(self.march, self.march_out) if self.march is not None else None,
+            mode=cfg.ray_marching_type, select_grids=cfg.depth_points or 0, feat_ref=self.feat_ref, shape=self.shape_nhwc,
+            defer_feats=defer_feats, feat_dtype=self.feature_dtype)
+
     def _trace(self):
         cfg, plan = self.cfg, self.plan
         plan.begin_static()
         out = {}
         with P.using(plan), torch.no_grad():
             side = None
-            if self.dense:
+            if self.dense and DENSE_BRANCH:
                 # the dense volume is an output of the scene (the Atlas 3D network's input), nothing downstream in the hot path
                 # reads it: DENSE_BRANCH runs it as a parallel branch of the graph (forked stream, joined at the end) -- off
                 # by default, see the note at the switch
-                main = torch.cuda.current_stream(self.device)
-                if DENSE_BRANCH:
-                    if getattr(self, "_side", None) is None:
-                        self._side = torch.cuda.Stream(device=self.device)
-                    side = self._side
-                    side.wait_stream(main)
-                with torch.cuda.stream(side if side is not None else main):
-                    out["volume"], out["count"] = rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin,
-                                                                        cfg.stride, proj_scaled=self.proj_scaled,
-                                                                        feat_ref=self.feat_ref, shape=self.shape_nhwc,
-                                                                        feat_dtype=self.feature_dtype,
-                                                                        workspace=self._dense_workspace())
-            fixed = cfg.sample_seed is not None          # a fixed seed: every replay draws the same subset (as forward_scene)
-            coords, feats, n_sel, info = rma.aggregate_points_static(
-                self.nhwc, self.proj_inv, self.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
-                max_points=cfg.max_points, seed=cfg.sample_seed if fixed else 0x5EED,
-                seed_dev=None if fixed else self.seed_dev,
-                marched=(self.march, self.march_out) if self.march is not None else None,
-                mode=cfg.ray_marching_type, select_grids=cfg.depth_points or 0, feat_ref=self.feat_ref, shape=self.shape_nhwc,
-                defer_feats=DEFER_POINT_FEATURES, feat_dtype=self.feature_dtype)
+                if self._side is None:
+                    self._side = torch.cuda.Stream(device=self.device)
+                side = self._side
+                side.wait_stream(torch.cuda.current_stream(self.device))
+            dense, coords, feats, n_sel, info = self._geometry(defer_feats=DEFER_POINT_FEATURES, side=side)
+            if dense is not None:
+                out["volume"], out["count"] = dense
             moved = coords + self.offset_dev     # ray_marching.py:364 (one fp32 add per coordinate, as the reference)
             out.update(trace_net(plan, self.backbone, self.head, moved, feats, n_sel, cfg.voxel_size_fcaf3d, self.device,
                                  extra_counts=[info["M"], n_sel], late=info, nms=self.nms, nms_state=self._nms_state))
-            if not fixed:
+            if cfg.sample_seed is None:
                 self.seed_dev.add_(1)            # the next replay draws a fresh point subset
             if side is not None:
                 torch.cuda.current_stream(self.device).wait_stream(side)          # join
@@ -581,32 +615,30 @@ class StaticScene:
         _lib.require_gpu()
         eager = None
         if plan is not None:
-            self.plan = P.Plan(self.margin)
-            self.plan.sizes, self.plan.flags, self.plan.marks = list(plan.sizes), list(plan.flags), dict(plan.marks)
+            self.plan = plan.copy()
         elif self.plan is None:
             eager = self.calibrate(features_nchw, projections, tsdf, proj_inv)
         self._enter(features_nchw, tsdf)
         with torch.cuda.stream(self.stream):
             self._alloc_inputs(features_nchw, tsdf)
             self._load(features_nchw, projections, tsdf, proj_inv)
-            self.out = self._trace()                         # plain static run: creates the trace's constants
-            self.stream.synchronize()
-            if capture:
-                try:                                             # keep_graph only serves the node count, a diagnostic
-                    self.graph, kept = torch.cuda.CUDAGraph(keep_graph=True), True
-                except TypeError:                                # a torch build without it: capture instantiates by itself
-                    self.graph, kept = torch.cuda.CUDAGraph(), False
-                with torch.cuda.graph(self.graph, stream=self.stream):
-                    self.out = self._trace()
-                self.n_nodes = graph_node_count(self.graph) if kept else None   # launches per scene (bench: graph_nodes_per_scene)
-                # tables of the CAPTURED trace that did not fit the 0xFF arena its sizing run measured (each clears itself: one
-                # launch more; 0 unless the two runs took different table sequences -- ADVICE round 5)
-                self.arena_fallbacks = self.plan.arena_fallbacks
-                if kept:
-                    self.graph.instantiate()
-                self.stream.synchronize()
+            self._capture(capture)
         self._tag = weights_tag(self._weights)
         return eager
+
+    def _record(self):
+        try:                                                 # keep_graph only serves the node count, a diagnostic
+            kept = torch.cuda.CUDAGraph(keep_graph=True)
+        except TypeError:                                    # a torch build without it: capture instantiates by itself
+            kept = None
+        super()._record(kept)
+        kept = kept is not None
+        self.n_nodes = graph_node_count(self.graph) if kept else None
+        # tables of the CAPTURED trace that did not fit the 0xFF arena its sizing run measured (each clears itself: one
+        # launch more; 0 unless the two runs took different table sequences -- ADVICE round 5)
+        self.arena_fallbacks = self.plan.arena_fallbacks
+        if kept:
+            self.graph.instantiate()
 
     def run(self, features_nchw, projections, tsdf, proj_inv=None, offset=None, by_reference=None):
         """enqueue one scene on self.stream (ordered behind the caller's current stream, which produced the inputs);
@@ -630,45 +662,28 @@ class StaticScene:
         with torch.cuda.stream(self.stream):
             self._load(features_nchw, projections, tsdf, proj_inv, offset, by_reference)
             consumed = self._consumed
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self.out = self._trace()
-            self.done = torch.cuda.Event()
-            self.done.record()
-        self.out["done"] = self.done
+            self._replay()
         # when the caller may write the feature maps again: by reference -> only after the whole scene
         self.out["inputs_consumed"] = self.done if self._held is not None else consumed
         return self.out
 
     def rebuild(self, features_nchw, projections, tsdf):
-        """fold the sizes of the scenes that outgrew the plan (detect()'s eager fall-backs) into the plan and trace /
-        capture again at the larger capacities"""
-        if getattr(self, "outgrown", None) is not None:
+        """fold the sizes of the scenes that outgrew the plan (the eager fall-backs) into the plan and trace / capture
+        again at the larger capacities"""
+        if self.outgrown is not None:
             self.plan.static = False
             self.plan = self.plan.merge(self.outgrown) if len(self.plan.sizes) == len(self.outgrown.sizes) else self.outgrown
             self.outgrown, self.n_outgrown = None, 0
-        fresh = P.Plan(self.margin)
-        fresh.sizes, fresh.flags, fresh.marks = list(self.plan.sizes), list(self.plan.flags), dict(self.plan.marks)
-        self.plan = None
-        return self.build(features_nchw, projections, tsdf, capture=True, plan=fresh)
+        return self.build(features_nchw, projections, tsdf, capture=True, plan=self.plan)
 
     @staticmethod
     def detections(out):
         """static outputs -> (bboxes [K,*], scores [K,n_cls], info) like forward_scene; ONE device->host read.  Raises
         when the scene violated an assumption of the plan (the caller re-runs it with forward_scene)."""
         L = len(out["sizes"])
-        if out.get("done") is not None:
-            torch.cuda.current_stream(out["bboxes"].device).wait_event(out["done"])
-        host = _lib.read_ints(torch.cat((out["status"].view(-1), out["valid"].view(-1), out["counts"].view(-1))))
-        if host[0] != 0:
-            raise _lib.CnrmaError(f"{host[0]} capacity / branch assumption(s) of the static plan violated: re-run eagerly")
-        valid, counts = host[1:1 + L], host[1 + L:]
-        rows, r0 = [], 0
-        for k, v in zip(out["sizes"], valid):
-            rows.append(torch.arange(r0, r0 + v, device=out["bboxes"].device))
-            r0 += k
-        rows = torch.cat(rows)
+        host = _read_back(out)
+        valid, counts = host[:L], host[L:]
+        rows = _live_rows(out["sizes"], valid, out["bboxes"].device)
         nl, ne = out["n_levels"], out.get("n_extra", 2)
         info = dict(M_unique=counts[ne], level_rows=counts[ne + 1:ne + 1 + nl], head_rows=counts[ne + 1 + nl:ne + 1 + 2 * nl])
         if ne == 2:
@@ -676,6 +691,20 @@ class StaticScene:
         return out["bboxes"].index_select(0, rows), out["scores"].index_select(0, rows), info
 
     final_detections = staticmethod(final_detections)
+
+    def fall_back(self, features_nchw, projections, tsdf, offset=None):
+        """a scene that outgrew the size plan, through the eager path on the current stream (forward_scene: the true sizes are
+        read back from the device); its sizes are kept in self.outgrown -- merged with those of earlier such scenes when they
+        recorded the same sequence, in their place otherwise -- for rebuild(), and n_outgrown counts it.  Returns the eager result."""
+        grown = P.Plan(self.margin)
+        with P.using(grown):
+            e = forward_scene(self.cfg, self.backbone, self.head, features_nchw, projections, tsdf, dense=self.dense,
+                              offset=_offset_list(offset), keep_half=self.feature_dtype != torch.float32)
+        prev = self.outgrown
+        same = prev is not None and len(prev.sizes) == len(grown.sizes) and len(prev.flags) == len(grown.flags)
+        self.outgrown = prev.merge(grown) if same else grown
+        self.n_outgrown += 1
+        return e
 
     def detect(self, features_nchw, projections, tsdf, rebuild_after=4, offset=None, by_reference=None):
         """run() + detections() with the fallback a server wants: a scene that outgrows the size plan (status != 0) is
@@ -691,14 +720,7 @@ class StaticScene:
             return b, s, info
         except _lib.CnrmaError:
             with torch.cuda.stream(self.stream):
-                grown = P.Plan(self.margin)
-                with P.using(grown):
-                    e = forward_scene(self.cfg, self.backbone, self.head, features_nchw, projections, tsdf, dense=self.dense,
-                                      offset=_offset_list(offset), keep_half=self.feature_dtype != torch.float32)
-            prev = getattr(self, "outgrown", None)
-            same = prev is not None and len(prev.sizes) == len(grown.sizes) and len(prev.flags) == len(grown.flags)
-            self.outgrown = prev.merge(grown) if same else grown
-            self.n_outgrown = getattr(self, "n_outgrown", 0) + 1
+                e = self.fall_back(features_nchw, projections, tsdf, offset)
             info = {k: e[k] for k in ("M", "M_selected", "M_unique", "level_rows", "head_rows")}
             info["static"] = False
             if rebuild_after and self.n_outgrown >= rebuild_after:
@@ -707,7 +729,7 @@ class StaticScene:
             return e["bboxes"], e["scores"], info
 
 
-class StaticBatch:
+class StaticBatch(_StaticGraph):
     """Several scenes per static pass: the geometric half (layout, dense unprojection, march, selection) per scene, then
     ONE collated multi-scene sparse tensor (batch id = scene, what ME.utils.batch_sparse_collate builds for B samples,
     ray_marching.py:328-330) through the backbone / neck / head, per-scene instance norm / pruning / decode with
@@ -718,13 +740,12 @@ class StaticBatch:
     half, n_scenes x the single-scene capacities for the network."""
 
     def __init__(self, cfg, backbone, head, device, n_scenes, margin=1.2, dense=True, stream=None):
+        super().__init__(device, margin, stream)
         self.cfg, self.backbone, self.head = cfg, backbone, head
-        self.device = torch.device(device)
-        self.B, self.margin, self.dense = int(n_scenes), margin, dense
-        self.stream = stream if stream is not None else torch.cuda.Stream(device=self.device)
-        # input holders: one StaticScene per scene of the pass, used for its static input buffers and its loader only
+        self.B, self.dense = int(n_scenes), dense
+        # input holders: one StaticScene per scene of the pass, used for its static input buffers, its loader and its
+        # geometric half only
         self.holders = [StaticScene(cfg, backbone, head, device, margin, dense, stream=self.stream) for _ in range(self.B)]
-        self.graph = self.plan = self.out = None
 
     def build(self, scenes, plan, capture=True):
         """scenes: B tuples (features_nchw, projections, tsdf[, offset]); plan: a calibrated single-scene Plan (merged over
@@ -732,24 +753,12 @@ class StaticBatch:
         _lib.require_gpu()
         assert len(scenes) == self.B
         self.plan = plan.scaled(self.B)
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.stream:                              # inputs written on the caller's stream just before build()
-            self.stream.wait_stream(cur)
-            for sc_ in scenes:
-                for t_ in (sc_[0], sc_[2]):
-                    if torch.is_tensor(t_) and t_.is_cuda:
-                        t_.record_stream(self.stream)
+        self._enter(*(t for sc_ in scenes for t in (sc_[0], sc_[2])))       # feature maps and TSDFs, written just before build()
         with torch.cuda.stream(self.stream):
             for h, sc_ in zip(self.holders, scenes):
                 h._alloc_inputs(sc_[0], sc_[2])
             self._load(scenes)
-            self.out = self._trace()
-            self.stream.synchronize()
-            if capture:
-                self.graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(self.graph, stream=self.stream):
-                    self.out = self._trace()
-                self.stream.synchronize()
+            self._capture(capture)
 
     def _load(self, scenes):
         for h, sc_ in zip(self.holders, scenes):
@@ -761,20 +770,12 @@ class StaticBatch:
         out = {}
         with P.using(plan), torch.no_grad():
             vols, pts, Ms = [], [], []
-            fixed = cfg.sample_seed is not None
             for b, h in enumerate(self.holders):                  # the geometric half, scene by scene
-                if self.dense:
-                    vols.append(rma.backproject_accum(None, None, cfg.dims, cfg.voxel_size, cfg.origin, cfg.stride,
-                                                      proj_scaled=h.proj_scaled, feat_ref=h.feat_ref, shape=h.shape_nhwc,
-                                                      workspace=h._dense_workspace()))
-                coords, feats, n_sel, info = rma.aggregate_points_static(
-                    h.nhwc, h.proj_inv, h.tsdf, cfg.dims, cfg.voxel_size, cfg.origin, cfg.n_steps, cfg.thr,
-                    max_points=cfg.max_points, seed=(cfg.sample_seed if fixed else 0x5EED) + 7919 * b * (0 if fixed else 1),
-                    seed_dev=None if fixed else h.seed_dev, marched=(h.march, h.march_out) if h.march is not None else None,
-                    mode=cfg.ray_marching_type, select_grids=cfg.depth_points or 0, feat_ref=h.feat_ref, shape=h.shape_nhwc)
+                dense, coords, feats, n_sel, info = h._geometry(seed=0x5EED + 7919 * b)
+                vols.append(dense)
                 pts.append((coords + h.offset_dev, feats, n_sel))
                 Ms += [info["M"].view(1), n_sel.view(1)]
-                if not fixed:
+                if cfg.sample_seed is None:
                     h.seed_dev.add_(1)
             x = S.sparse_collate_static(pts, cfg.voxel_size_fcaf3d)
             levels = self.backbone(x)
@@ -791,42 +792,20 @@ class StaticBatch:
 
     def run(self, scenes):
         """enqueue one pass of B scenes on self.stream; returns the static output dict (valid until the next run)"""
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self.stream:
-            self.stream.wait_stream(cur)
-            for sc_ in scenes:
-                for t_ in (sc_[0], sc_[2]):
-                    if torch.is_tensor(t_) and t_.is_cuda:
-                        t_.record_stream(self.stream)
+        self._enter(*(t for sc_ in scenes for t in (sc_[0], sc_[2])))
         with torch.cuda.stream(self.stream):
             self._load(scenes)
-            if self.graph is not None:
-                self.graph.replay()
-            else:
-                self.out = self._trace()
-            self.done = torch.cuda.Event()
-            self.done.record()
-        self.out["done"] = self.done
-        return self.out
+            return self._replay()
 
     def detections(self, out):
         """static outputs -> [(bboxes, scores, info)] per scene; ONE device->host read for the whole pass"""
         B, L = self.B, len(out["sizes"])
-        if out.get("done") is not None:
-            torch.cuda.current_stream(self.device).wait_event(out["done"])
-        host = _lib.read_ints(torch.cat((out["status"].view(-1), out["valid"].view(-1), out["counts"].view(-1))))
-        if host[0] != 0:
-            raise _lib.CnrmaError(f"{host[0]} capacity / branch assumption(s) of the static plan violated: re-run eagerly")
-        valid = host[1:1 + B * L]
-        counts = host[1 + B * L:]
+        host = _read_back(out)
+        valid, counts = host[:B * L], host[B * L:]
         nl = out["n_levels"]
         res = []
         for b in range(B):
-            rows, r0 = [], 0
-            for k, v in zip(out["sizes"], valid[b * L:(b + 1) * L]):
-                rows.append(torch.arange(r0, r0 + v, device=self.device))
-                r0 += k
-            rows = torch.cat(rows)
+            rows = _live_rows(out["sizes"], valid[b * L:(b + 1) * L], self.device)
             lv = counts[2 * B + B:]                               # after (M, M_sel) x B and the B unique counts
             info = dict(M=counts[2 * b], M_selected=counts[2 * b + 1], M_unique=counts[2 * B + b],
                         level_rows=[lv[l * B + b] for l in range(nl)], head_rows=[lv[(nl + l) * B + b] for l in range(nl)])

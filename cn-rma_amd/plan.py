@@ -87,16 +87,21 @@ class Plan:
         if not self.static:
             self.marks[name] = (len(self.sizes), len(self.flags))
 
+    def copy(self):
+        """a fresh recording plan with this plan's margin, slack and records (sizes, flags, marks, in containers of its own) and
+        none of its trace state: what another graph of the same configuration is traced and captured under"""
+        p = Plan(self.margin, self.slack)
+        p.sizes, p.flags, p.marks = list(self.sizes), list(self.flags), dict(self.marks)
+        return p
+
     def scaled(self, n_scenes, split="net"):
         """the plan of a pass over `n_scenes` scenes derived from this single-scene plan: the records before the mark
         (the per-scene geometric half: one aggregation, one voxelisation per scene) are consumed once per scene, entry
         by entry; the records behind it (the network over the collated tensor) scale with the number of scenes"""
         i, j = self.marks[split]
         assert j == 0, "per-scene stages record sizes only"
-        p = Plan(self.margin, self.slack)
+        p = self.copy()
         p.sizes = [s for s in self.sizes[:i] for _ in range(n_scenes)] + [s * n_scenes for s in self.sizes[i:]]
-        p.flags = list(self.flags)
-        p.marks = dict(self.marks)
         return p
 
     def record_flag(self, f):

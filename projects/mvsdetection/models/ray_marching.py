@@ -396,7 +396,7 @@ class RayMarching(MultiViewBase):
                                          dense=dense_in_graph, by_reference=self.static_feature_handoff == "reference",
                                          feature_dtype=fdt, nms=self.static_nms)
             ctx = dict(cfg=cfg, slots=[first], pending=[None] * max(1, self.static_slots), seen=0, k=0, built=False,
-                       weights=pipeline.weight_tensors(self.detection_backbone, self.detection_head), tag=None, grown=0)
+                       weights=pipeline.weight_tensors(self.detection_backbone, self.detection_head), tag=None)
             self._static[key] = ctx
         if not ctx["built"]:
             # calibration scenes: the eager path produces their results (files, module state) exactly as before; a second,
@@ -440,7 +440,7 @@ class RayMarching(MultiViewBase):
             self.volume = out["volume"].unsqueeze(0)
             self.__dict__["_lazy_valid"] = (out["count"], out["done"])
         self.__dict__["_lazy_points"] = out
-        item = dict(st=st, out=out, scene=scene, inputs=(feats, proj, tsdf, offset), finished=threading.Event(), status=None,
+        item = dict(out=out, scene=scene, inputs=(feats, proj, tsdf, offset), finished=threading.Event(), status=None,
                     result=None)
         ctx["pending"][i] = item
         self._writer_queue().put(item)                          # {scene}_bbox_raw.npz is written as soon as the scene has left the GPU
@@ -460,7 +460,7 @@ class RayMarching(MultiViewBase):
                                       nms=first.nms)
             st.build(feats, proj, tsdf, plan=first.plan)
             ctx["slots"].append(st)
-        ctx["built"], ctx["grown"] = True, 0
+        ctx["built"] = True
         ctx["tag"] = pipeline.weights_tag(ctx["weights"])
 
     # ---- results leave the device on a writer thread: a scene's file exists as soon as its graph has finished ---------------
@@ -521,15 +521,14 @@ class RayMarching(MultiViewBase):
                 # (tens of GB at the north-star shape) alive after `del model` (round 6: bench.py's resident memory)
                 item = out = model = b = s = final = None
 
-    def _drain(self, ctx, i):
+    def _drain(self, ctx, i, rebuild=True):
         """the slot's previous scene has left its static buffers (its file is written) -- or, if it outgrew the size plan,
-        is re-run eagerly here; after 4 such scenes the plan is enlarged by their sizes and the graphs are captured again"""
+        is re-run eagerly here (StaticScene.fall_back of the context's first slot, which keeps the sizes and the count);
+        after 4 such scenes the plan is enlarged by their sizes and the graphs are captured again"""
         item = ctx["pending"][i]
         if item is None:
             return
         ctx["pending"][i] = None
-        from cnrma_amd import pipeline
-        from cnrma_amd import plan as P
         item["finished"].wait()
         if item["status"] == "ok":
             b, s = item["result"]
@@ -539,33 +538,19 @@ class RayMarching(MultiViewBase):
             raise item["error"]
         self.static_fallbacks = getattr(self, "static_fallbacks", 0) + 1
         feats, proj, tsdf, offset = item["inputs"]
-        st = item["st"]
-        grown = P.Plan(st.margin)
-        with P.using(grown):                                    # the eager pass reads the true sizes back and records them
-            e = pipeline.forward_scene(ctx["cfg"], self.detection_backbone, self.detection_head, feats, proj, tsdf,
-                                       offset=pipeline._offset_list(offset), dense=st.dense,
-                                       keep_half=st.feature_dtype != torch.float32)
+        first = ctx["slots"][0]
+        e = first.fall_back(feats, proj, tsdf, offset)          # the eager pass reads the true sizes back and records them
         self._save_raw(e["bboxes"], e["scores"], item["scene"])
-        prev = ctx.get("outgrown")
-        same = prev is not None and len(prev.sizes) == len(grown.sizes) and len(prev.flags) == len(grown.flags)
-        ctx["outgrown"] = prev.merge(grown) if same else grown
-        ctx["grown"] += 1
-        if ctx["grown"] >= 4:                                   # a deployment whose scenes grew: stop paying replay + eager per scene
+        if rebuild and first.n_outgrown >= 4:                   # a deployment whose scenes grew: stop paying replay + eager per scene
             for j in range(len(ctx["pending"])):
                 if j != i:
                     self._drain_no_rebuild(ctx, j)
-            first = ctx["slots"][0]
-            first.outgrown, first.n_outgrown = ctx.pop("outgrown"), ctx["grown"]
             first.rebuild(feats, proj, tsdf)
-            self._build_slots(ctx, feats, proj, tsdf, st.dense, first_is_built=True)
+            self._build_slots(ctx, feats, proj, tsdf, first.dense, first_is_built=True)
             self.static_rebuilds = getattr(self, "static_rebuilds", 0) + 1
 
     def _drain_no_rebuild(self, ctx, j):
-        g, ctx["grown"] = ctx["grown"], -10 ** 6               # scenes drained on the way to a rebuild never trigger another one
-        try:
-            self._drain(ctx, j)
-        finally:
-            ctx["grown"] = g
+        self._drain(ctx, j, rebuild=False)                      # scenes drained on the way to a rebuild never trigger another one
 
     def flush(self):
         """wait until the detections of every scene still in flight are written (called when the eager path takes over, on

@@ -358,3 +358,121 @@ def test_copy_hand_off_lets_the_producer_overwrite_its_buffer(device):
     assert st2._held is None
     b2, s2, _ = pipeline.StaticScene.detections(out2)
     assert torch.equal(out2["volume"], vol0) and torch.equal(b2, b0) and torch.equal(s2, s0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the lifecycle the three graph objects share: traced without capture, an outgrown plan, ordering behind the producer
+# ---------------------------------------------------------------------------------------------------------------------
+_BATCH_CASE = {}
+
+
+def _batch_case(device):
+    """two tiny scenes, the small model, their calibrated single-scene plan and what the CAPTURED batch returns for them
+    (out, detections): computed once, read by the tests below and left unchanged"""
+    if not _BATCH_CASE:
+        from cnrma_amd import pipeline
+        scenes = []
+        for i in range(2):
+            sc, feat, proj, tsdf = _scene("tiny", 10 + i, device, boxes=i)
+            scenes.append((feat, proj, tsdf, torch.tensor([0.1 * i, -0.2 * i, 0.05])))
+        backbone, head = _model(scenes[0][0].shape[1], device)
+        head.pts_threshold = 1500
+        cfg = pipeline.SceneConfig(sc["dims"], stride=sc["stride"], max_points=20000, sample_seed=4321)
+        cal = pipeline.StaticScene(cfg, backbone, head, device)
+        for f, p, t, o in scenes:
+            cal.calibrate(f, p, t, offset=o)
+        batch = pipeline.StaticBatch(cfg, backbone, head, device, 2)
+        batch.build(scenes, cal.plan)
+        assert batch.graph is not None
+        out = batch.run(scenes)
+        res = batch.detections(out)
+        ref = dict(volume=[v.clone() for v in out["volume"]], count=[c.clone() for c in out["count"]],
+                   dets=[(b.clone(), s.clone(), info) for b, s, info in res])
+        _BATCH_CASE.update(scenes=scenes, model=(backbone, head), cfg=cfg, plan=cal.plan, ref=ref)
+    return _BATCH_CASE
+
+
+def _assert_batch_equals_reference(out, res, ref):
+    for i, ((b, s, info), (b0, s0, info0)) in enumerate(zip(res, ref["dets"])):
+        assert info == info0, (i, info, info0)
+        assert torch.equal(out["volume"][i], ref["volume"][i]) and torch.equal(out["count"][i], ref["count"][i])
+        assert torch.equal(b, b0) and torch.equal(s, s0)
+
+
+def test_static_batch_traced_without_capture_equals_the_captured_batch(device):
+    """capture=False: run() goes through the launch sequence itself instead of a graph replay -- the same kernels on the same
+    capacities, so the same bits: info, dense volumes and counts, boxes and scores of both scenes"""
+    from cnrma_amd import pipeline
+    case = _batch_case(device)
+    batch = pipeline.StaticBatch(case["cfg"], *case["model"], device, 2)
+    batch.build(case["scenes"], case["plan"], capture=False)
+    assert batch.graph is None
+    batch.run(list(reversed(case["scenes"])))                            # other inputs through the trace first
+    out = batch.run(case["scenes"])
+    _assert_batch_equals_reference(out, batch.detections(out), case["ref"])
+
+
+def test_static_batch_flags_scenes_that_outgrow_the_plan(device):
+    """a plan cut to a quarter of the calibrated sizes (no slack, no margin): every kernel of the pass stays inside its
+    capacities, detections() raises, and another batch on the true plan serves the same scenes with the same results"""
+    from cnrma_amd import _lib, pipeline
+    from cnrma_amd import plan as P
+    case = _batch_case(device)
+    small = P.Plan(1.0, 0)
+    small.sizes = [max(1, n // 4) for n in case["plan"].sizes]
+    small.flags, small.marks = list(case["plan"].flags), dict(case["plan"].marks)
+    batch = pipeline.StaticBatch(case["cfg"], *case["model"], device, 2)
+    batch.build(case["scenes"], small)
+    out = batch.run(case["scenes"])
+    with pytest.raises(_lib.CnrmaError):
+        batch.detections(out)
+    torch.cuda.synchronize()
+    good = pipeline.StaticBatch(case["cfg"], *case["model"], device, 2)
+    good.build(case["scenes"], case["plan"])
+    out = good.run(case["scenes"])
+    _assert_batch_equals_reference(out, good.detections(out), case["ref"])
+
+
+@pytest.mark.parametrize("kind", ["net", "batch"])
+def test_net_and_batch_order_themselves_behind_the_producer_stream(device, kind):
+    """what test_run_orders_itself_behind_the_producer_stream (test_static_oracle_gpu.py) checks for StaticScene, for the other
+    two graph objects: inputs written late on the caller's stream, right before run(), and freed right after it"""
+    from cnrma_amd import pipeline
+    case = _batch_case(device)
+    backbone, head = case["model"]
+    if kind == "batch":
+        obj = pipeline.StaticBatch(case["cfg"], backbone, head, device, 2)
+        obj.build(case["scenes"], case["plan"])
+        inputs = [case["scenes"][0][0], case["scenes"][1][0]]                # the two scenes' feature maps
+
+        def run(fresh):
+            out = obj.run([(f,) + sc_[1:] for f, sc_ in zip(fresh, case["scenes"])])
+            return out, lambda: [r[0] for r in obj.detections(out)] + list(out["volume"])
+    else:
+        rng = np.random.RandomState(3)
+        pts = rng.rand(6000, 3).astype(np.float32) * np.array([1.0, 0.8, 0.6], dtype=np.float32)
+        pts[:2000, 2] = 0.01 * rng.rand(2000)                                # a floor and a wall: surfaces, like a scene
+        pts[2000:4000, 0] = 1.0 - 0.01 * rng.rand(2000)
+        C = case["scenes"][0][0].shape[1]
+        inputs = [torch.from_numpy(pts).to(device), torch.from_numpy(rng.randn(6000, C).astype(np.float32)).to(device)]
+        obj = pipeline.StaticNet(backbone, head, 0.01, device)
+        obj.build(*inputs)
+
+        def run(fresh):
+            out = obj.run(*fresh)
+            return out, lambda: [pipeline.StaticScene.detections(out)[0]]
+    assert obj.graph is not None
+    _, read = run(inputs)
+    torch.cuda.synchronize()
+    ref = [t.clone() for t in read()]
+    big = torch.randn(4096, 4096, device=device)
+    for _ in range(3):
+        junk = big @ big                                       # keeps the default stream busy for a while
+        fresh = [(x * 3.0 / 3.0 * 1.0 + junk[0, 0] * 0.0) for x in inputs]
+        fresh = [(x + (y - y)).contiguous() for x, y in zip(inputs, fresh)]     # == inputs, but fresh allocations written just now
+        _, read = run(fresh)
+        del fresh                                              # the allocator may hand the blocks out again right away
+        scratch = [torch.full_like(x, 7.0) for x in inputs]
+        got = read()
+        assert len(got) == len(ref) and all(torch.equal(a, b) for a, b in zip(got, ref))
+        del scratch
