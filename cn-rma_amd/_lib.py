@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip.so")
 EXP_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip_exp.so")
 
-P, I, L, F = c_void_p, c_int, c_int64, c_float
+P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
 
 # name -> (restype, argtypes); mirrors include/cnrma.h one to one
 SIGNATURES = {
@@ -139,6 +139,13 @@ SIGNATURES = {
     "cnrma_mesh_workspace_bytes": (c_size_t, [I, I, I]),
     "cnrma_mesh_count_f32": (c_int, [P, I, I, I, P, c_size_t, P, P]),
     "cnrma_mesh_emit_f32": (c_int, [P, I, I, I, F, P, P, P, P, L, P, L, P, P]),
+    "cnrma_cloud_downsample_workspace_bytes": (c_size_t, [L]),
+    "cnrma_cloud_voxel_downsample_f32": (c_int, [P, L, P, D, P, c_size_t, P, P, L, P, P]),
+    "cnrma_cloud_nn_workspace_bytes": (c_size_t, [L]),
+    "cnrma_cloud_nn_build_f32": (c_int, [P, L, P, D, P, c_size_t, P]),
+    "cnrma_cloud_nn_query_f32": (c_int, [P, L, P, L, P, P, P, P, P]),
+    "cnrma_cloud_score_workspace_bytes": (c_size_t, [L]),
+    "cnrma_cloud_score_f64": (c_int, [P, L, P, D, P, c_size_t, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -851,6 +851,53 @@ int cnrma_mesh_emit_f32(const float* tsdf, int X, int Y, int Z, float voxel_size
                         const void* workspace, float* vertices, float* normals, int64_t v_cap, int32_t* faces, int64_t f_cap,
                         const int32_t* counts, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * a15  point clouds: voxel down-sample, exact nearest neighbour, metric sums   replaces eval_mesh / nn_correspondance
+ *      (post_process/evaluate_mesh.py:29-92: Open3D's voxel_down_sample and a KDTreeFlann queried vertex by vertex from Python).
+ * Points are [N][3] fp32, row-major.  Row counts are (n_cap, n_dev): the first min(n_cap, n_dev[0]) rows are live (n_dev DEVICE
+ *   word; NULL = n_cap rows); dead rows may hold anything (NaN included) and are never read.  n_cap <= 2^31 - 2.  No entry point
+ *   allocates, synchronises or reads the environment; clears are kernel launches; workspaces are 16-byte aligned and their sizes
+ *   (host arithmetic, 0 = rejected arguments) are functions of n_cap alone.
+ *
+ * cnrma_cloud_voxel_downsample_f32: Open3D's voxel_down_sample.  lo[a] = fp32 minimum of coordinate a over the live points;
+ *   org[a] = (double)lo[a] - 0.5 * voxel_size; k[a] = floor(((double)p[a] - org[a]) / voxel_size) in fp64 with IEEE division,
+ *   un-fused; a voxel is a distinct triple k; its point is (float)(sum of (double)p / count) per axis, the fp64 sum taken in
+ *   ascending input index.  Voxels come out in ascending (kx, ky, kz) (Open3D: hash-map order).  out_points [out_cap][3] fp32,
+ *   out_count [out_cap] int32 (may be NULL), info[4] (DEVICE) = {number of voxels, flags, 0, 0}.  Rows at or beyond out_cap are
+ *   never written; info[0] still holds the true need.  flags: CNRMA_CLOUD_NONFINITE (a live coordinate is NaN or +-inf),
+ *   CNRMA_CLOUD_VOXEL_TOO_SMALL (some k[a] >= 2^21: Open3D's "voxel_size is too small"); with a flag up no row is written and
+ *   info[0] = 0.  n_cap = 0 (or no live row): 0 voxels, no flags.
+ *
+ * cnrma_cloud_nn_build_f32: a uniform grid over the live targets in `workspace` (cnrma_cloud_nn_workspace_bytes(n_cap)): the
+ *   bounding box, then one thread derives the cell size (`cell`, enlarged by steps of 1.125 until the grid has <= 2^24 cells) and
+ *   the dims into a device header; targets sorted by cell (z fastest) as 16-byte records {x, y, z, index} and a CSR of cell
+ *   starts.  Targets with a non-finite coordinate, or none at all, give a grid of one cell.
+ * cnrma_cloud_nn_query_f32: for every live query q the target t that minimises d2 = (dx*dx + dy*dy) + dz*dz, dx = (double)q.x -
+ *   (double)t.x and likewise y, z: fp64, un-fused, in this bracket order; ties go to the lowest target index (the index into the
+ *   caller's array).  dist [nq_cap] fp64 = sqrt(d2), idx [nq_cap] int32; no live target: dist = +inf, idx = -1.  Rows behind the
+ *   live queries are not written.  The result is a function of the two clouds alone: it does not depend on `cell`, the grid or
+ *   the visiting order (shells of cells around the query's cell, until the best is strictly nearer than every unvisited cell can
+ *   be).  nt_cap: the n_cap of the build (it places the workspace's parts).  stats (DEVICE uint64 [2], may be NULL; the caller
+ *   clears it): += {shells visited, candidates scored} over the live queries -- for measurement, the outputs are the same.
+ *
+ * cnrma_cloud_score_f64: out3[0] = sum of dist over the live rows (cnrma_sum_f64: one fixed order), out3[1] = number of live
+ *   rows with dist < threshold (fp64, strict), out3[2] = number of live rows; all three as fp64 (DEVICE).
+ * ---------------------------------------------------------------------------------------------------------- */
+#define CNRMA_CLOUD_NONFINITE 1
+#define CNRMA_CLOUD_VOXEL_TOO_SMALL 2
+size_t cnrma_cloud_downsample_workspace_bytes(int64_t n_cap);
+int cnrma_cloud_voxel_downsample_f32(const float* points, int64_t n_cap, const int32_t* n_dev, double voxel_size,
+                                     void* workspace, size_t workspace_bytes, float* out_points, int32_t* out_count,
+                                     int64_t out_cap, int32_t* info, void* stream);
+size_t cnrma_cloud_nn_workspace_bytes(int64_t n_cap);
+int cnrma_cloud_nn_build_f32(const float* targets, int64_t n_cap, const int32_t* n_dev, double cell, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int cnrma_cloud_nn_query_f32(const float* queries, int64_t nq_cap, const int32_t* nq_dev, int64_t nt_cap,
+                             const void* workspace, double* dist, int32_t* idx, uint64_t* stats, void* stream);
+size_t cnrma_cloud_score_workspace_bytes(int64_t n_cap);
+int cnrma_cloud_score_f64(const double* dist, int64_t n_cap, const int32_t* n_dev, double threshold, void* workspace,
+                          size_t workspace_bytes, double* out3, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
