@@ -146,6 +146,8 @@ SIGNATURES = {
     "cnrma_cloud_nn_query_f32": (c_int, [P, L, P, L, P, P, P, P, P]),
     "cnrma_cloud_score_workspace_bytes": (c_size_t, [L]),
     "cnrma_cloud_score_f64": (c_int, [P, L, P, D, P, c_size_t, P, P]),
+    "cnrma_tsdf_fuse_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, I, F, F, F, P, P, P, P, P]),
+    "cnrma_tsdf_fuse_finish_f32": (c_int, [P, P, P, L, P, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -898,6 +898,39 @@ size_t cnrma_cloud_score_workspace_bytes(int64_t n_cap);
 int cnrma_cloud_score_f64(const double* dist, int64_t n_cap, const int32_t* n_dev, double threshold, void* workspace,
                           size_t workspace_bytes, double* out3, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * a16  TSDF fusion: posed depth maps into running volumes   replaces TSDFFusion.integrate / get_tsdf
+ *      (data_prepare/scannet/tsdf.py:353-474, fed one frame at a time by generate_tsdf.py:104-126; data_prepare/arkit/tsdf.py holds
+ *      the same class).  The pinned behaviour is the reference on the CPU, bit for bit, for every voxel.
+ * Volumes are flat [N], N = X*Y*Z < 2^31, index (x Y + y) Z + z; images are row-major [H][W], H and W < 2^24.
+ *
+ * cnrma_tsdf_fuse_f32 (tsdf.py:402-451): integrates views 0 .. V-1 in index order, in place, in ONE launch: a lane owns a voxel and
+ *   keeps its six running values in registers across the views, so the volumes are read and written once per launch.
+ *   proj [V][12] (row-major 3x4), depth [V][H][W], color [V][3][H][W] or NULL, label [V][H][W] int32 or NULL, origin3_dev [3]:
+ *   all DEVICE.  tsdf [N], weight [N], color_vol [3][N] or NULL, label_vol [N] int32 or NULL: DEVICE, in/out (a fresh state is
+ *   tsdf 1, weight 0, colour 0, label -1).  All arithmetic is fp32, un-fused unless written as fma:
+ *     w_a  = (float)index_a * voxel_size + origin[a]                          (product rounded, then the sum; tsdf.py:376)
+ *     cam_r = fma(P[r][3], 1, fma(P[r][2], wz, fma(P[r][1], wy, P[r][0] * wx)))            (tsdf.py:413 as the CPU's sgemm evaluates it)
+ *     px = rint(cam_0 / cam_2), py = rint(cam_1 / cam_2) (IEEE division, ties to even), pz = cam_2            (tsdf.py:414-416)
+ *     valid = 0 <= px < W and 0 <= py < H and pz > 0, compared as floats (NaN and +-inf fail, -0 passes)              (tsdf.py:420)
+ *     d = depth[v][py][px]; d > max_depth -> d = 0 (generate_tsdf.py:119; +inf disables it); valid needs d > 0        (tsdf.py:424)
+ *     dist = max((pz - d) / trunc_margin, -1) with a true division (a NaN stays a NaN); valid needs dist < 1     (tsdf.py:427-433)
+ *     near = valid and dist > -1                                                                                      (tsdf.py:442)
+ *     weight == 0 and valid: tsdf = dist (also when dist == -1: the weight stays 0 and a later view overwrites it again;
+ *     tsdf.py:437-438); else near: tsdf += dist (tsdf.py:444-445).  near: weight += 1, color_vol[c] += color[v][c][py][px],
+ *     label_vol = label[v][py][px] (the newest wins; tsdf.py:446-451).  weight == 0 is read before the view's own increment.
+ *   color / label NULL: that volume is not touched (color_vol / label_vol may then be NULL too).  -22 for a negative size, N >= 2^31,
+ *   H or W >= 2^24, color without color_vol, label without label_vol, or a NULL required pointer; V == 0 or N == 0 (or an image
+ *   without pixels) is a no-op.  No atomics, no allocation, no synchronisation, nothing read from the environment.
+ * cnrma_tsdf_fuse_finish_f32 (tsdf.py:453-474, get_tsdf): tsdf_out[i] = weight[i] > 0 ? tsdf[i] / weight[i] : tsdf[i], and the same
+ *   for the three planes of color_vol -> color_out [3][n]; either output may be NULL.  The running volumes are only read.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cnrma_tsdf_fuse_f32(const float* proj, const float* depth, const float* color, const int32_t* label,
+                        const float* origin3_dev, int V, int H, int W, int X, int Y, int Z, float voxel_size, float trunc_margin,
+                        float max_depth, float* tsdf, float* weight, float* color_vol, int32_t* label_vol, void* stream);
+int cnrma_tsdf_fuse_finish_f32(const float* tsdf, const float* weight, const float* color_vol, int64_t n, float* tsdf_out,
+                               float* color_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,25 +18,32 @@ def coordinates(voxel_dim, device=None):
 
 
 class TSDF:
-    def __init__(self, voxel_size, origin, tsdf_vol):
-        """voxel_size in metres, origin [1,3] = position of voxel (0,0,0), tsdf_vol [nx,ny,nz]"""
+    def __init__(self, voxel_size, origin, tsdf_vol, attribute_vols=None):
+        """voxel_size in metres, origin [1,3] = position of voxel (0,0,0), tsdf_vol [nx,ny,nz]; attribute_vols: further voxel
+        volumes by name (what cnrma_amd.fusion.TSDFFusion.get_tsdf fills in: 'color' [3,nx,ny,nz], 'instance' [nx,ny,nz])"""
         self.voxel_size = voxel_size
         self.origin = origin
         self.tsdf_vol = tsdf_vol
+        self.attribute_vols = {} if attribute_vols is None else attribute_vols
         self.device = tsdf_vol.device
 
     def save(self, fname):
+        """the reference's npz (data_prepare/scannet/tsdf.py:140-148): origin, voxel_size, tsdf and one key per attribute volume"""
+        attrs = {k: v.detach().cpu().numpy() for k, v in self.attribute_vols.items()}
         np.savez_compressed(fname, origin=self.origin.cpu().numpy(), voxel_size=self.voxel_size,
-                            tsdf=self.tsdf_vol.detach().cpu().numpy())
+                            tsdf=self.tsdf_vol.detach().cpu().numpy(), **attrs)
 
     @classmethod
     def load(cls, fname):
+        """reads 'color' and 'instance' beside the volume when the file holds them (data_prepare/scannet/tsdf.py:150-177)"""
         with np.load(fname) as z:
-            return cls(z["voxel_size"].item(), torch.as_tensor(z["origin"]).view(1, 3), torch.as_tensor(z["tsdf"]))
+            attrs = {k: torch.as_tensor(z[k]) for k in ("color", "instance") if k in z}
+            return cls(z["voxel_size"].item(), torch.as_tensor(z["origin"]).view(1, 3), torch.as_tensor(z["tsdf"]), attrs)
 
     def to(self, device):
         self.origin = self.origin.to(device)
         self.tsdf_vol = self.tsdf_vol.to(device)
+        self.attribute_vols = {k: v.to(device) for k, v in self.attribute_vols.items()}
         self.device = device
         return self
 
