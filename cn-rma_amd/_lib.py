@@ -234,6 +234,35 @@ def call(name, *args):
     return rc
 
 
+def scratch(query_name, *args, device, dtype=None):
+    """a fresh buffer of as many bytes as the library's `query_name(*args)` asks for (uint8; another dtype: that many bytes in
+    whole elements).  Never cached: the allocator's stream ordering is what makes reuse of the block safe"""
+    import torch
+    nbytes = getattr(load(), query_name)(*args)
+    if dtype is None:
+        return torch.empty(nbytes, dtype=torch.uint8, device=device)
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=device)
+
+
+LRU_STREAMS = 12      # entries a stream-keyed table keeps by default: the streams of a process come and go (every scene slot / detector
+                      # has its own), their raw handles are all such a table knows of them -- the least recently used entries are
+                      # dropped (round 6: ~1 GB per detector ever built stayed allocated).  Dropping is safe: the caching allocator
+                      # hands a freed block back to the stream it was allocated on, in stream order.
+LRU_LOCK = threading.RLock()      # the tables are module-wide; several host threads (one per scene slot) reach them
+
+
+def lru_get(table, key, make, limit=LRU_STREAMS):
+    """table[key] (moved to the most-recent end), created by make() when absent; the oldest entries beyond `limit` are dropped"""
+    with LRU_LOCK:
+        buf = table.pop(key, None)
+        if buf is None:
+            buf = make()
+        table[key] = buf
+        while len(table) > limit:
+            table.pop(next(iter(table)))
+        return buf
+
+
 _tls = threading.local()
 
 

@@ -32,10 +32,10 @@ def _points(p, device=None):
 
 
 def _workspace(name, n, dev):
-    nbytes = getattr(_lib.load(), name)(n)
-    if nbytes == 0:
+    ws = _lib.scratch(name, n, device=dev)
+    if ws.numel() == 0:
         raise _lib.CnrmaError(f"{name}: unsupported row count {n}")
-    return torch.empty(nbytes, dtype=torch.uint8, device=dev), nbytes
+    return ws
 
 
 def _down_sample(pts, voxel_size, n_dev=None):
@@ -44,8 +44,8 @@ def _down_sample(pts, voxel_size, n_dev=None):
     dev = pts.device
     out = torch.empty((n, 3), dtype=torch.float32, device=dev)
     info = torch.empty(4, dtype=torch.int32, device=dev)
-    ws, nbytes = _workspace("cnrma_cloud_downsample_workspace_bytes", n, dev)
-    call("cnrma_cloud_voxel_downsample_f32", ptr(pts) if n else None, n, ptr(n_dev), float(voxel_size), ptr(ws), nbytes,
+    ws = _workspace("cnrma_cloud_downsample_workspace_bytes", n, dev)
+    call("cnrma_cloud_voxel_downsample_f32", ptr(pts) if n else None, n, ptr(n_dev), float(voxel_size), ptr(ws), ws.numel(),
          ptr(out) if n else None, None, n, ptr(info), stream())
     return out, info
 
@@ -82,10 +82,10 @@ def nearest(queries, targets, cell=None, *, nq_dev=None, nt_dev=None, stats=None
     cell = 0.04 if cell is None else float(cell)
     if not cell > 0:
         raise ValueError(f"cell must be positive, got {cell}")
-    ws, nbytes = _workspace("cnrma_cloud_nn_workspace_bytes", nt, dev)
+    ws = _workspace("cnrma_cloud_nn_workspace_bytes", nt, dev)
     dist = torch.empty(nq, dtype=torch.float64, device=dev)
     idx = torch.empty(nq, dtype=torch.int32, device=dev)
-    call("cnrma_cloud_nn_build_f32", ptr(t) if nt else None, nt, ptr(nt_dev), cell, ptr(ws), nbytes, stream())
+    call("cnrma_cloud_nn_build_f32", ptr(t) if nt else None, nt, ptr(nt_dev), cell, ptr(ws), ws.numel(), stream())
     if nq:
         call("cnrma_cloud_nn_query_f32", ptr(q), nq, ptr(nq_dev), nt, ptr(ws), ptr(dist), ptr(idx), ptr(stats), stream())
     return dist, idx
@@ -93,8 +93,8 @@ def nearest(queries, targets, cell=None, *, nq_dev=None, nt_dev=None, stats=None
 
 def _score(dist, n_dev, threshold, out3):
     n = int(dist.shape[0])
-    ws, nbytes = _workspace("cnrma_cloud_score_workspace_bytes", n, dist.device)
-    call("cnrma_cloud_score_f64", ptr(dist) if n else None, n, ptr(n_dev), float(threshold), ptr(ws), nbytes, ptr(out3), stream())
+    ws = _workspace("cnrma_cloud_score_workspace_bytes", n, dist.device)
+    call("cnrma_cloud_score_f64", ptr(dist) if n else None, n, ptr(n_dev), float(threshold), ptr(ws), ws.numel(), ptr(out3), stream())
 
 
 def default_cell(threshold=.05, down_sample=.02):

@@ -70,12 +70,11 @@ def marching_cubes(tsdf_vol, voxel_size=1.0, origin=None):
         org = torch.zeros(3, dtype=torch.float32, device=dev)
     else:
         org = torch.as_tensor(origin, dtype=torch.float32).reshape(3).to(dev).contiguous()
-    nbytes = _lib.load().cnrma_mesh_workspace_bytes(X, Y, Z)
-    if nbytes == 0:
+    ws = _lib.scratch("cnrma_mesh_workspace_bytes", X, Y, Z, device=dev)
+    if ws.numel() == 0:
         raise _lib.CnrmaError(f"marching_cubes: unsupported volume shape {(X, Y, Z)}")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     counts = torch.empty(4, dtype=torch.int32, device=dev)
-    call("cnrma_mesh_count_f32", ptr(vol), X, Y, Z, ptr(ws), nbytes, ptr(counts), stream())
+    call("cnrma_mesh_count_f32", ptr(vol), X, Y, Z, ptr(ws), ws.numel(), ptr(counts), stream())
     nv, nf = _lib.read_ints(counts)[:2]
     vertices = torch.empty((nv, 3), dtype=torch.float32, device=dev)
     normals = torch.empty((nv, 3), dtype=torch.float32, device=dev)

@@ -54,16 +54,15 @@ class MinkowskiConvolution(nn.Module):
         if torch.is_grad_enabled() and (x.F.requires_grad or self.kernel.requires_grad):
             # fused epilogue requested while gradients are wanted (eval-mode fine-tuning with frozen BatchNorm, input-gradient
             # analysis): the fused kernel has no backward -- the same result through the differentiable convolution + torch
-            y = S.conv_autograd(x, self.kernel, self.kernel_size, self.stride).F
+            out = S.conv_autograd(x, self.kernel, self.kernel_size, self.stride)
+            y = out.F
             if scale is not None:
                 y = y * scale.view(1, -1)
             if shift is not None:
                 y = y + shift.view(1, -1)
             if residual is not None:
                 y = y + (residual.F if isinstance(residual, S.SparseTensor) else residual)
-            y = torch.relu(y) if act == "relu" else (nn.functional.elu(y) if act == "elu" else y)
-            out_cs = x.cs if self.stride == 1 else x.cs.strided(self.stride)
-            return S.SparseTensor(y, out_cs)
+            return S.SparseTensor(S._act_torch(y, act), out.cs)
         return S.conv(x, self.kernel, self.kernel_size, self.stride, scale, shift, residual, act)
 
 
@@ -123,8 +122,7 @@ class MinkowskiBatchNorm(nn.Module):
             y = x.F * scale + shift
         if residual is not None:
             y = y + residual.F
-        y = nn.functional.elu(y) if relu == "elu" else (torch.relu(y) if relu else y)
-        return S.SparseTensor(y, x.cs)
+        return S.SparseTensor(S._act_torch(y, relu), x.cs)
 
 
 class MinkowskiInstanceNorm(nn.Module):

@@ -75,8 +75,7 @@ def nms_device_buffers(n_cap, n_cls, cols, device, out_cap=None):
     """workspace and outputs of one nms_device() call site (a static trace allocates them once and hands them in as `out=`);
     out_cap defaults to n_cap * n_cls, which no input overflows"""
     out_cap = n_cap * n_cls if out_cap is None else int(out_cap)
-    need = _lib.load().cnrma_nms_classes_workspace_bytes(n_cap, n_cls)
-    return dict(workspace=torch.empty(max(need, 16), dtype=torch.uint8, device=device),
+    return dict(workspace=_lib.scratch("cnrma_nms_classes_workspace_bytes", n_cap, n_cls, device=device),      # >= 32 bytes for n_cls >= 1
                 boxes=torch.zeros((out_cap, cols), dtype=torch.float32, device=device),
                 scores=torch.zeros((out_cap,), dtype=torch.float32, device=device),
                 labels=torch.zeros((out_cap,), dtype=torch.long, device=device),

@@ -177,13 +177,8 @@ def _dense_workspace(dev, st, nbytes=0):
     was captured with."""
     nbytes = max(int(nbytes), DENSE_WORKSPACE_BYTES)
     key = (dev.index if dev.index is not None else torch.cuda.current_device(), st, nbytes)
-    ws = _DENSE_WS.get(key)
-    if ws is None:
-        if len(_DENSE_WS) >= 64:                  # streams come and go; their handles are all this table knows of them
-            _DENSE_WS.pop(next(iter(_DENSE_WS)))
-        ws = torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev)
-        _DENSE_WS[key] = ws
-    return ws
+    # streams come and go; their handles are all this table knows of them: the 64 most recently used blocks stay
+    return _lib.lru_get(_DENSE_WS, key, lambda: torch.zeros((nbytes + 3) // 4, dtype=torch.int32, device=dev), limit=64)
 
 
 def dense_tuning(**kw):
@@ -339,8 +334,7 @@ class _March:
         if tab is not None:      # sigmoid(-tsdf) once per voxel instead of once per marched step (bit-identical) + the free-space
             if (self.R >= MARCH_SKIP_MIN_RAYS) if MARCH_SKIP == "auto" else bool(MARCH_SKIP):   # skip table (radius per 4^3 block)
                 if getattr(self, "_skip", None) is None:
-                    self._skip = torch.empty(_lib.load().cnrma_rma_skip_table_bytes(self.X, self.Y, self.Z), dtype=torch.uint8,
-                                             device=self.dev)
+                    self._skip = _lib.scratch("cnrma_rma_skip_table_bytes", self.X, self.Y, self.Z, device=self.dev)
                 skip = self._skip
             call("cnrma_rma_march_tables_f32", ptr(self.tsdf), self.X, self.Y, self.Z, ptr(tab), ptr(skip), stream())
         tail = (ptr(self.pinv), ptr(self.tsdf), ptr(tab), self.V, self.H, self.W, self.X, self.Y, self.Z, self.vs, *self.org,
@@ -378,18 +372,21 @@ class _March:
     def emit_rows(self, row_offset, n_out, kept, sel_index, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat,
                   feat_stride, out_sample=None, n_out_dev=None):
         """n_out = rows of the output buffers; n_out_dev = device word with the live row count (None: all n_out)"""
-        rec = torch.empty((int(n_out), 4), dtype=torch.int32, device=self.dev)
-        call(*self._emit_rows_head(), self.V, self.C, self.H, self.W, self.N,
-             self.t_one, ptr(row_offset), int(n_out), ptr(n_out_dev), ptr(kept), kept.shape[1], ptr(sel_index),
-             sel_index.numel() if sel_index is not None else 0, ptr(rec), ptr(w_div), float(add[0]),
-             float(add[1]), float(add[2]), out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride, ptr(out_sample),
-             stream())
+        rec = torch.empty((int(n_out), 4), dtype=torch.int32, device=self.dev)      # the kernel makes the records itself
+        self._emit_rows(row_offset, kept, sel_index, rec, n_out, n_out_dev, w_div, add, out_xyz, xyz_stride, out_w, w_stride,
+                        out_feat, feat_stride, out_sample)
 
     def emit_records(self, rec, n_out, n_out_dev, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride,
                      out_sample=None):
         """emit_rows for records that are already selected and placed (select_records)"""
+        self._emit_rows(None, None, None, rec, n_out, n_out_dev, w_div, add, out_xyz, xyz_stride, out_w, w_stride, out_feat,
+                        feat_stride, out_sample)
+
+    def _emit_rows(self, row_offset, kept, sel_index, rec, n_out, n_out_dev, w_div, add, out_xyz, xyz_stride, out_w, w_stride,
+                   out_feat, feat_stride, out_sample):
         call(*self._emit_rows_head(), self.V, self.C, self.H, self.W, self.N,
-             self.t_one, None, int(n_out), ptr(n_out_dev), None, 0, None, 0, ptr(rec), ptr(w_div), float(add[0]),
+             self.t_one, ptr(row_offset), int(n_out), ptr(n_out_dev), ptr(kept), kept.shape[1] if kept is not None else 0,
+             ptr(sel_index), sel_index.numel() if sel_index is not None else 0, ptr(rec), ptr(w_div), float(add[0]),
              float(add[1]), float(add[2]), out_xyz, xyz_stride, out_w, w_stride, out_feat, feat_stride, ptr(out_sample),
              stream())
 
@@ -410,7 +407,7 @@ def exclusive_scan(count):
     """int32 [n] -> int32 [n+1] exclusive prefix sums (last entry = total), on the device."""
     n = count.numel()
     out = torch.empty(n + 1, dtype=torch.int32, device=count.device)
-    ws = torch.empty(_lib.load().cnrma_scan_workspace_bytes(n), dtype=torch.uint8, device=count.device)
+    ws = _lib.scratch("cnrma_scan_workspace_bytes", n, device=count.device)
     call("cnrma_exclusive_scan_i32", ptr(count), ptr(out), n, ptr(ws), stream())
     return out
 
@@ -420,7 +417,7 @@ def mask_to_index(mask_u8):
     n = mask_u8.numel()
     sel = torch.empty(n, dtype=torch.int32, device=mask_u8.device)
     n_sel = torch.empty(1, dtype=torch.int32, device=mask_u8.device)
-    ws = torch.empty(_lib.load().cnrma_scan_workspace_bytes(n), dtype=torch.uint8, device=mask_u8.device)
+    ws = _lib.scratch("cnrma_scan_workspace_bytes", n, device=mask_u8.device)
     call("cnrma_mask_to_index", ptr(mask_u8), ptr(sel), ptr(n_sel), n, ptr(ws), stream())
     return sel, n_sel
 
@@ -428,15 +425,20 @@ def mask_to_index(mask_u8):
 _SAMPLE_CALLS = [0]
 
 
+def _next_seed():
+    """the seed of a sampling call that names none: advances per call, deterministic under torch.manual_seed"""
+    _SAMPLE_CALLS[0] += 1
+    return (0x9E3779B9 * _SAMPLE_CALLS[0] + int(torch.initial_seed())) & 0xFFFFFFFF
+
+
 def sample_mask_device(m_dev, M, n_keep, seed=None, seed_dev=None):
     """uint8 [M] keep-mask with exactly min(m, n_keep) ones among the first m = min(m_dev[0], M) rows (zeros behind):
     a uniformly random subset drawn ON THE DEVICE (device-side stand-in for sample_points' np.random.choice;
     deterministic in `seed`, advancing per call when seed is None; seed_dev: device word mixed into the seed)."""
     if seed is None:
-        _SAMPLE_CALLS[0] += 1
-        seed = (0x9E3779B9 * _SAMPLE_CALLS[0] + int(torch.initial_seed())) & 0xFFFFFFFF
+        seed = _next_seed()
     mask = torch.empty(M, dtype=torch.uint8, device=m_dev.device)
-    ws = torch.empty(_lib.load().cnrma_sample_workspace_bytes(), dtype=torch.uint8, device=m_dev.device)
+    ws = _lib.scratch("cnrma_sample_workspace_bytes", device=m_dev.device)
     call("cnrma_sample_mask", m_dev.data_ptr(), M, int(n_keep), int(seed), ptr(seed_dev), ptr(mask), ptr(ws), stream())
     return mask
 
@@ -445,17 +447,15 @@ def select_records(row_offset, kept, m_dev, M, n_keep, rec_cap, seed=None, seed_
     """sample_mask_device + mask_to_index + the record scatter in one go, per ray (cnrma_rma_select_records): the same random
     subset, records int32 [rec_cap, 4] = {ray, step, weight bits, 0} in row order and their number n_sel int32 [1]"""
     if seed is None:
-        _SAMPLE_CALLS[0] += 1
-        seed = (0x9E3779B9 * _SAMPLE_CALLS[0] + int(torch.initial_seed())) & 0xFFFFFFFF
+        seed = _next_seed()
     dev = m_dev.device
     R = row_offset.numel() - 1
-    lib = _lib.load()
     rec = torch.empty((int(rec_cap), 4), dtype=torch.int32, device=dev)
     n_sel = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(lib.cnrma_sample_workspace_bytes(), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("cnrma_sample_workspace_bytes", device=dev)
     cnt = torch.empty(R, dtype=torch.int32, device=dev)
     off = torch.empty(R + 1, dtype=torch.int32, device=dev)
-    sws = torch.empty(lib.cnrma_scan_workspace_bytes(R), dtype=torch.uint8, device=dev)
+    sws = _lib.scratch("cnrma_scan_workspace_bytes", R, device=dev)
     call("cnrma_rma_select_records", ptr(row_offset), R, ptr(kept), kept.shape[1], m_dev.data_ptr(), int(M), int(n_keep),
          int(seed), ptr(seed_dev), ptr(ws), ptr(cnt), ptr(off), ptr(sws), int(rec_cap), ptr(rec), ptr(n_sel), stream())
     return rec, n_sel
@@ -529,18 +529,25 @@ def aggregate_begin(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_s
         cnt, wsum, kept, overflow = m.march()
     else:
         cnt, wsum = m.count()
+    off, m_total, mean_w = _row_offsets(m, cnt, wsum, reference_quirks)
+    readback = torch.cat((m_total, overflow)) if single_march else m_total
+    return dict(m=m, single_march=single_march, cnt=cnt, off=off, kept=kept, mean_w=mean_w, m_total=m_total,
+                readback=readback)
+
+
+def _row_offsets(m, cnt, wsum, reference_quirks):
+    """from the march's per-ray counts and weight sums: (off int32 [R+1] = first row of every ray, m_total = off[R:], the device
+    word with the row count, mean_w float [1] = the mean weight over all rows), after the reference's one-sample quirk"""
     if reference_quirks:
         _drop_single_sample_views(cnt, wsum, m.V)
     off = exclusive_scan(cnt)
-    ws = torch.empty(_lib.load().cnrma_scan_workspace_bytes(m.R), dtype=torch.uint8, device=m.dev)
+    ws = _lib.scratch("cnrma_scan_workspace_bytes", m.R, device=m.dev)
     wtot = torch.empty(1, dtype=torch.float64, device=m.dev)
     mean_w = torch.empty(1, dtype=torch.float32, device=m.dev)
     call("cnrma_sum_f64", ptr(wsum), ptr(wtot), m.R, ptr(ws), stream())
     m_total = off[m.R:]
     call("cnrma_rma_mean_weight", ptr(wtot), m_total.data_ptr(), ptr(mean_w), stream())
-    readback = torch.cat((m_total, overflow)) if single_march else m_total
-    return dict(m=m, single_march=single_march, cnt=cnt, off=off, kept=kept, mean_w=mean_w, m_total=m_total,
-                readback=readback)
+    return off, m_total, mean_w
 
 
 def aggregate_finish(st, readback, offset=(0.0, 0.0, 0.0), max_points=None, sampler="numpy", mask=None, seed=None):
@@ -612,15 +619,7 @@ def aggregate_points_static(features_nhwc, proj_inv, tsdf, dims, voxel_size, ori
         if m.kept_cap() <= 0:
             raise _lib.CnrmaError("the static trace needs the single-march NeuS path (thr > 1/62)")
         cnt, wsum, kept, overflow = m.march()
-    if reference_quirks:
-        _drop_single_sample_views(cnt, wsum, m.V)
-    off = exclusive_scan(cnt)
-    ws = torch.empty(_lib.load().cnrma_scan_workspace_bytes(m.R), dtype=torch.uint8, device=m.dev)
-    wtot = torch.empty(1, dtype=torch.float64, device=m.dev)
-    mean_w = torch.empty(1, dtype=torch.float32, device=m.dev)
-    call("cnrma_sum_f64", ptr(wsum), ptr(wtot), m.R, ptr(ws), stream())
-    m_total = off[m.R:]
-    call("cnrma_rma_mean_weight", ptr(wtot), m_total.data_ptr(), ptr(mean_w), stream())
+    off, m_total, mean_w = _row_offsets(m, cnt, wsum, reference_quirks)
     rows_per_ray = max(1, 2 * m.k) if depth else kept.shape[1]
     M_cap = plan.next_cap(bound=m.R * rows_per_ray, n_dev=m_total, lo=1)      # lo = 1: M == 0 is the reference's TypeError
     if overflow is not None:

@@ -175,7 +175,7 @@ class CoordSet:
         src_C, src_ndev, cap = cs.C, cs.n_dev, cs.n
         if levels <= 0 or cap == 0:
             return
-        ws = torch.empty(_lib.load().cnrma_voxelize_workspace_bytes(cap), dtype=torch.uint8, device=self.device)
+        ws = _lib.scratch("cnrma_voxelize_workspace_bytes", cap, device=self.device)
         plan = P.current()
         if plan is not None and plan.static:
             # static trace: every level gets its planned capacity (hash table sized for it); the coordinate buffer keeps
@@ -277,7 +277,7 @@ def tile_union(in_cs, out_set, kernel_size, offset_stride):
     tu = in_cs._union.get(key)
     if tu is None:
         nbr = in_cs.neighbours(out_set, kernel_size, offset_stride)
-        tu = torch.empty(_lib.load().cnrma_sparse_tile_union_bytes(out_set.n), dtype=torch.uint8, device=in_cs.device)
+        tu = _lib.scratch("cnrma_sparse_tile_union_bytes", out_set.n, device=in_cs.device)
         call("cnrma_sparse_tile_union_build", ptr(nbr), out_set.n, ptr(out_set.n_dev), nbr.shape[1], ptr(tu), stream())
         in_cs._union[key] = tu
     return tu
@@ -370,7 +370,7 @@ def _voxelize_enqueue(coords, feats, voxel_size, batch_id, row_order, m_dev=None
         out_f = torch.empty((M, C), dtype=torch.float32, device=dev)
     src = torch.empty(M, dtype=torch.int32, device=dev)
     n_out = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(_lib.load().cnrma_voxelize_workspace_bytes(M), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("cnrma_voxelize_workspace_bytes", M, device=dev)
     call("cnrma_voxelize_f32", ptr(coords), ptr(feats), M, ptr(m_dev), C, float(voxel_size), int(batch_id),
          {"first": 0, "morton": 1}[row_order], ptr(m.keys), ptr(m.vals),
          m.cap, ptr(out_c), ptr(out_f), ptr(src), out_cap, ptr(n_out), ptr(ws), stream())
@@ -471,28 +471,9 @@ def fold_bn(bn, bias=None):
     return scale.contiguous().float(), shift.contiguous().float()
 
 
-ACT = {None: 0, "none": 0, "relu": 1, "elu": 2}
+ACT = {None: 0, "none": 0, False: 0, "relu": 1, True: 1, "elu": 2}      # activation code of the C-ABI (False / True: batch_norm_train's relu flag)
 
-_WS = {}
-_WS_STREAMS = 12      # scratch buffers kept: the streams of a process come and go (every scene slot / detector has its own), their
-                      # raw handles are all this table knows of them -- the least recently used entries are dropped (round 6: ~1 GB
-                      # per detector ever built stayed allocated).  Dropping is safe: the caching allocator hands a freed block
-                      # back to the stream it was allocated on, in stream order.
-
-
-_LRU_LOCK = threading.RLock()      # the tables are module-wide; several host threads (one per scene slot) reach them
-
-
-def _lru_get(table, key, make, limit=_WS_STREAMS):
-    """table[key] (moved to the most-recent end), created by make() when absent; the oldest entries beyond `limit` are dropped"""
-    with _LRU_LOCK:
-        buf = table.pop(key, None)
-        if buf is None:
-            buf = make()
-        table[key] = buf
-        while len(table) > limit:
-            table.pop(next(iter(table)))
-        return buf
+_WS = {}                  # (device, stream) -> buffer, least recently used first (_lib.lru_get)
 
 
 def _workspace(nbytes, device):
@@ -501,11 +482,11 @@ def _workspace(nbytes, device):
     if P.static():
         return P.current().workspace(nbytes, device)
     key = (device, stream())
-    with _LRU_LOCK:
+    with _lib.LRU_LOCK:
         buf = _WS.pop(key, None)
         if buf is None or buf.numel() < nbytes:
             buf = torch.empty(max(nbytes, 1 << 20), dtype=torch.uint8, device=device)
-        return _lru_get(_WS, key, lambda: buf)
+        return _lib.lru_get(_WS, key, lambda: buf)
 
 
 _COUNTER_WORDS = 16384
@@ -523,7 +504,7 @@ def _tile_counters(device):
     if P.static():
         return P.current().counters(device, _COUNTER_WORDS)
     key = (device, stream())
-    return _lru_get(_COUNTERS, key, lambda: torch.zeros(_COUNTER_WORDS, dtype=torch.int32, device=device))
+    return _lib.lru_get(_COUNTERS, key, lambda: torch.zeros(_COUNTER_WORDS, dtype=torch.int32, device=device))
 
 
 # "f16x3":  22-bit operands on the fp16 matrix cores: a 2^s = h + m (two fp16 pieces, power-of-two scale from the tensor's
@@ -611,7 +592,7 @@ def _weight_image(weight, kind, nbytes, entry, *args):
     if w.dim() == 2:
         w = w.unsqueeze(0)
     K, Cin, Cout = w.shape
-    ws = torch.empty(getattr(_lib.load(), nbytes)(K, Cin, Cout), dtype=torch.uint8, device=w.device)
+    ws = _lib.scratch(nbytes, K, Cin, Cout, device=w.device)
     call(entry, ptr(w), K, Cin, Cout, *args, ptr(ws), stream())
     _cache_put(weight, kind, (tag, ws))
     return _pinned(ws)
@@ -654,16 +635,15 @@ def weights_bf16_frag(weight, transposed=False):
         return _pinned(tr if transposed else fwd)
     w = weight.detach().contiguous().float()
     K, Cin, Cout = w.shape
-    lib = _lib.load()
     if Cin % 32 == 0 and Cout % 32 == 0 and Cin >= 64 and fwd is None and tr is None:
-        fwd = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
-        tr = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cout, Cin), dtype=torch.uint8, device=w.device)
+        fwd = _lib.scratch("cnrma_sparse_conv_bf16_frag_weight_bytes", K, Cin, Cout, device=w.device)
+        tr = _lib.scratch("cnrma_sparse_conv_bf16_frag_weight_bytes", K, Cout, Cin, device=w.device)
         call("cnrma_sparse_conv_prepare_weights_bf16_frag_pair", ptr(w), K, Cin, Cout, 1, ptr(fwd), ptr(tr), stream())
     elif transposed:
-        tr = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cout, Cin), dtype=torch.uint8, device=w.device)
+        tr = _lib.scratch("cnrma_sparse_conv_bf16_frag_weight_bytes", K, Cout, Cin, device=w.device)
         call("cnrma_sparse_conv_prepare_weights_bf16_frag", ptr(w), K, Cin, Cout, 1, 1, ptr(tr), stream())
     else:
-        fwd = torch.empty(lib.cnrma_sparse_conv_bf16_frag_weight_bytes(K, Cin, Cout), dtype=torch.uint8, device=w.device)
+        fwd = _lib.scratch("cnrma_sparse_conv_bf16_frag_weight_bytes", K, Cin, Cout, device=w.device)
         call("cnrma_sparse_conv_prepare_weights_bf16_frag", ptr(w), K, Cin, Cout, 0, 0, ptr(fwd), stream())
     _cache_put(weight, "_cnrma_bf16_frag", (tag, fwd, tr))
     return _pinned(tr if transposed else fwd)
@@ -784,6 +764,19 @@ def _nearly_empty_map(in_cs, out_cs):
     return f
 
 
+def _conv_sets(x, weight, kernel_size, stride):
+    """geometry of a convolution of x: (in_cs, out_cs, nbr, K, symmetric, sets).  nbr = None: the identity (1x1x1, stride 1);
+    symmetric: one coordinate set on both sides and an odd kernel (the data gradient may mirror the table); sets = (in_cs,
+    out_cs, kernel_size) of a 27-offset table, what the gather-once kernels key their tile unions on (None otherwise).
+    Inside a plan strided() and neighbours() draw capacities in call order: strided first, nothing in between."""
+    K = kernel_size ** 3
+    assert (weight.shape[0] if weight.dim() == 3 else 1) == K
+    in_cs = x.cs
+    out_cs = in_cs if stride == 1 else in_cs.strided(stride)
+    nbr = None if (kernel_size == 1 and stride == 1) else in_cs.neighbours(out_cs, kernel_size, in_cs.stride)
+    return in_cs, out_cs, nbr, K, out_cs is in_cs and kernel_size % 2 == 1, (in_cs, out_cs, kernel_size) if K == 27 else None
+
+
 def conv(x, weight, kernel_size=3, stride=1, scale=None, shift=None, residual=None, act=None, precision=None):
     """MinkowskiConvolution + fused epilogue: out = act((sum_k in[nbr] @ W[k]) * scale + shift + residual).
     weight [K,Cin,Cout] (or [Cin,Cout] when K == 1)."""
@@ -792,13 +785,8 @@ def conv(x, weight, kernel_size=3, stride=1, scale=None, shift=None, residual=No
     if w.dim() == 2:
         w = w.unsqueeze(0)
     K, Cin, Cout = w.shape
-    assert K == kernel_size ** 3 and Cin == x.F.shape[1]
-    in_cs = x.cs
-    out_cs = in_cs if stride == 1 else in_cs.strided(stride)
-    if kernel_size == 1 and stride == 1:
-        nbr = None
-    else:
-        nbr = in_cs.neighbours(out_cs, kernel_size, in_cs.stride)
+    assert Cin == x.F.shape[1]
+    in_cs, out_cs, nbr, _, _, _ = _conv_sets(x, w, kernel_size, stride)
     out = torch.empty((out_cs.n, Cout), dtype=torch.float32, device=x.device)
     out_split = out_amax = None
     if out_cs.n:
@@ -936,7 +924,7 @@ def _dgrad_weights(w3, flip, precision):
     from W (one kernel; the image cannot be cached -- the optimiser changes W every step), else the fp32 tensor"""
     K, Cin, Cout = w3.shape
     if precision == "bf16" and Cout % 32 == 0:
-        img = torch.empty(_lib.load().cnrma_sparse_conv_bf16_weight_bytes(K, Cout, Cin), dtype=torch.uint8, device=w3.device)
+        img = _lib.scratch("cnrma_sparse_conv_bf16_weight_bytes", K, Cout, Cin, device=w3.device)
         call("cnrma_sparse_conv_prepare_weights_bf16_t", ptr(w3.contiguous()), K, Cin, Cout, 1 if flip else 0, ptr(img), stream())
         return (K, Cout, Cin), img
     wt = (w3.flip(0) if flip else w3).transpose(1, 2).contiguous()
@@ -1088,32 +1076,15 @@ class _ConvBnActFn(torch.autograd.Function):
                 running_mean, running_var, batches):
         ctx.nbr, ctx.n_out, ctx.precision, ctx.symmetric, ctx.sets = nbr, n_out, _precision(precision), symmetric, sets
         y0 = _conv_fwd(ctx, F, weight)                           # the BatchNorm's input
-        n, C = y0.shape
-        out = torch.empty_like(y0)
-        ws = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=y0.device)
         w = bn_w.detach().contiguous().view(-1).float()
-        b = bn_b.detach().contiguous().view(-1).float()
-        r = residual.detach().contiguous().float() if residual is not None else None
-        call("cnrma_bn_train_forward_f32", ptr(y0), n, C, ptr(w), ptr(b), float(eps), ptr(r), act, float(momentum),
-             ptr(running_mean), ptr(running_var), ptr(batches), ptr(out), ptr(ws), stream())
+        out = _bn_train_fwd(ctx, y0, w, bn_b, residual, eps, act, momentum, running_mean, running_var, batches)
         ctx.save_for_backward(F, weight, y0, w, out if act else None)
-        ctx.eps, ctx.ws, ctx.has_res, ctx.act = float(eps), ws, residual is not None, act
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         F, weight, y0, w, y = ctx.saved_tensors
-        n, C = y0.shape
-        g = grad_out.contiguous().float()
-        dx = torch.empty_like(y0)
-        dres = torch.empty_like(y0) if ctx.has_res and y is not None else None
-        dw = torch.empty(C, dtype=torch.float32, device=y0.device)
-        db = torch.empty(C, dtype=torch.float32, device=y0.device)
-        ws2 = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=y0.device)
-        call("cnrma_bn_train_backward_f32", ptr(g), ptr(y0), ptr(y), ctx.act, n, C, ptr(ctx.ws), ptr(w), ctx.eps, ptr(dx), ptr(dres),
-             ptr(dw), ptr(db), ptr(ws2), stream())
-        if ctx.has_res and dres is None:
-            dres = g
+        dx, dw, db, dres = _bn_train_bwd(ctx, grad_out, y0, y, w)
         grad_F, grad_W = _conv_bwd(ctx, F, weight, dx, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         return (grad_F, grad_W, dw, db, dres) + (None,) * 11
 
@@ -1123,27 +1094,18 @@ FUSE_CONV_BN = True     # training: conv -> BatchNorm -> [+ shortcut] -> activat
 
 def conv_bn_act_train(x, weight, bn, kernel_size=3, stride=1, act=None, residual=None, precision=None):
     """training-mode conv -> bn -> [+ residual.F] -> act (None / "relu" / "elu") on SparseTensor x; one autograd node when
-    the fused BatchNorm takes the shape (see batch_norm_train), the composition of conv_autograd and batch_norm_train else"""
+    the fused BatchNorm takes the shape (_bn_hip_takes) and there are two output rows or more, the composition of conv_autograd
+    and batch_norm_train else"""
     _lib.require_gpu()
-    Cout = weight.shape[-1]
     res_f = None if residual is None else residual.F
-    if (not FUSE_CONV_BN or not BN_TRAIN_HIP or Cout > 256 or Cout % 4 or not bn.affine or not bn.track_running_stats
-            or bn.momentum is None or (res_f is not None and res_f.dtype != torch.float32)):
-        y = conv_autograd(x, weight, kernel_size, stride, precision)
-        return SparseTensor(batch_norm_train(y.F, bn, act if act else False, res_f), y.cs)
-    K = kernel_size ** 3
-    in_cs = x.cs
-    out_cs = in_cs if stride == 1 else in_cs.strided(stride)
-    if out_cs.n < 2:
-        y = conv_autograd(x, weight, kernel_size, stride, precision)
-        return SparseTensor(batch_norm_train(y.F, bn, act if act else False, res_f), y.cs)
-    nbr = None if (kernel_size == 1 and stride == 1) else in_cs.neighbours(out_cs, kernel_size, in_cs.stride)
-    assert (weight.shape[0] if weight.dim() == 3 else 1) == K
-    out = _ConvBnActFn.apply(x.F, weight, bn.weight, bn.bias, res_f, nbr, out_cs.n, precision,
-                             out_cs is in_cs and kernel_size % 2 == 1, (in_cs, out_cs, kernel_size) if K == 27 else None,
-                             bn.eps, {None: 0, "relu": 1, "elu": 2}[act], bn.momentum, bn.running_mean, bn.running_var,
-                             bn.num_batches_tracked)
-    return SparseTensor(out, out_cs)
+    if FUSE_CONV_BN and _bn_hip_takes(weight.shape[-1], bn, res_f):
+        in_cs, out_cs, nbr, _, symmetric, sets = _conv_sets(x, weight, kernel_size, stride)
+        if out_cs.n >= 2:
+            out = _ConvBnActFn.apply(x.F, weight, bn.weight, bn.bias, res_f, nbr, out_cs.n, precision, symmetric, sets, bn.eps,
+                                     ACT[act], bn.momentum, bn.running_mean, bn.running_var, bn.num_batches_tracked)
+            return SparseTensor(out, out_cs)
+    y = conv_autograd(x, weight, kernel_size, stride, precision)       # (the sets and the table are cached on x.cs by now)
+    return SparseTensor(batch_norm_train(y.F, bn, act if act else False, res_f), y.cs)
 
 
 def _wgrad_go(ctx, K, Cin, Cout):
@@ -1165,14 +1127,8 @@ def _wgrad_go(ctx, K, Cin, Cout):
 def conv_autograd(x, weight, kernel_size=3, stride=1, precision=None):
     """differentiable MinkowskiConvolution (no fused epilogue): gradients flow to x.F and to the weight"""
     _lib.require_gpu()
-    K = kernel_size ** 3
-    in_cs = x.cs
-    out_cs = in_cs if stride == 1 else in_cs.strided(stride)
-    nbr = None if (kernel_size == 1 and stride == 1) else in_cs.neighbours(out_cs, kernel_size, in_cs.stride)
-    assert (weight.shape[0] if weight.dim() == 3 else 1) == K
-    out = _ConvFn.apply(x.F, weight, nbr, out_cs.n, precision, out_cs is in_cs and kernel_size % 2 == 1,
-                        (in_cs, out_cs, kernel_size) if K == 27 else None)
-    return SparseTensor(out, out_cs)
+    _, out_cs, nbr, _, symmetric, sets = _conv_sets(x, weight, kernel_size, stride)
+    return SparseTensor(_ConvFn.apply(x.F, weight, nbr, out_cs.n, precision, symmetric, sets), out_cs)
 
 
 def _train(*tensors):
@@ -1181,7 +1137,9 @@ def _train(*tensors):
 
 
 def _act_torch(f, act):
-    return torch.relu(f) if act == "relu" else (torch.nn.functional.elu(f) if act == "elu" else f)
+    """the activation `act` (a key of ACT) through torch"""
+    code = ACT[act]
+    return torch.relu(f) if code == 1 else (torch.nn.functional.elu(f) if code == 2 else f)
 
 
 def conv_transpose_generative(x, weight, scale=None, shift=None, act=None, precision=None):
@@ -1293,7 +1251,7 @@ def instance_norm_max_pool(x, weight=None, bias=None, eps=1e-8, relu=True, kerne
     _lib.require_gpu()
     n, C = x.F.shape
     assert x.cs.n_batch <= 1 and C % 4 == 0 and not _train(x.F, weight, bias)
-    ws = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=x.device)
+    ws = _lib.scratch("cnrma_instnorm_workspace_bytes", C, device=x.device, dtype=torch.float64)
     w = weight.contiguous().view(-1).float() if weight is not None else None
     b = bias.contiguous().view(-1).float() if bias is not None else None
     src = x.F.contiguous()
@@ -1316,7 +1274,7 @@ def instance_norm(x, weight=None, bias=None, eps=1e-8, relu=False):
     _lib.require_gpu()
     n, C = x.F.shape
     out = torch.empty_like(x.F)
-    ws = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=x.device)
+    ws = _lib.scratch("cnrma_instnorm_workspace_bytes", C, device=x.device, dtype=torch.float64)
     w = weight.contiguous().view(-1).float() if weight is not None else None
     b = bias.contiguous().view(-1).float() if bias is not None else None
     if _train(x.F, weight, bias):    # training: per-scene statistics in torch
@@ -1374,47 +1332,66 @@ class _BatchNormTrainFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, F, weight, bias, residual, eps, relu, momentum, running_mean, running_var, batches):
         Fd = F.detach().contiguous().float()
-        n, C = Fd.shape
-        out = torch.empty_like(Fd)
-        ws = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=Fd.device)
         w = weight.detach().contiguous().view(-1).float()
-        b = bias.detach().contiguous().view(-1).float()
-        r = residual.detach().contiguous().float() if residual is not None else None
-        act = {False: 0, None: 0, True: 1, "relu": 1, "elu": 2}[relu]
-        call("cnrma_bn_train_forward_f32", ptr(Fd), n, C, ptr(w), ptr(b), float(eps), ptr(r), act, float(momentum),
-             ptr(running_mean), ptr(running_var), ptr(batches), ptr(out), ptr(ws), stream())
-        ctx.save_for_backward(Fd, w, out if act else None)
-        ctx.eps, ctx.ws, ctx.has_res, ctx.act = float(eps), ws, residual is not None, act      # ws[:2C]: mean, biased variance (fp64)
+        out = _bn_train_fwd(ctx, Fd, w, bias, residual, eps, ACT[relu], momentum, running_mean, running_var, batches)
+        ctx.save_for_backward(Fd, w, out if ctx.act else None)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         Fd, w, y = ctx.saved_tensors
-        n, C = Fd.shape
-        g = grad_out.contiguous().float()
-        dx = torch.empty_like(Fd)
-        dres = torch.empty_like(Fd) if ctx.has_res and y is not None else None
-        dw = torch.empty(C, dtype=torch.float32, device=Fd.device)
-        db = torch.empty(C, dtype=torch.float32, device=Fd.device)
-        ws2 = torch.empty(_lib.load().cnrma_instnorm_workspace_bytes(C) // 8, dtype=torch.float64, device=Fd.device)
-        call("cnrma_bn_train_backward_f32", ptr(g), ptr(Fd), ptr(y), ctx.act, n, C, ptr(ctx.ws), ptr(w), ctx.eps, ptr(dx), ptr(dres),
-             ptr(dw), ptr(db), ptr(ws2), stream())
-        if ctx.has_res and dres is None:
-            dres = g                                    # no ReLU: the residual branch takes the incoming gradient as it is
-        return dx, dw, db, dres, None, None, None, None, None, None
+        return _bn_train_bwd(ctx, grad_out, Fd, y, w) + (None,) * 6
+
+
+def _bn_train_fwd(st, x, w, b, residual, eps, act, momentum, running_mean, running_var, batches):
+    """out = act( bn(x) [+ residual] ) by cnrma_bn_train_forward_f32.  x fp32 [n, C] contiguous, w = the weight flat and fp32 (the
+    caller saves it), b = the bias as the module holds it, act = the C-ABI's code (ACT); st: an autograd ctx, which receives
+    eps, ws (ws[:2C]: mean, biased variance in fp64), has_res and act for _bn_train_bwd"""
+    n, C = x.shape
+    out = torch.empty_like(x)
+    ws = _lib.scratch("cnrma_instnorm_workspace_bytes", C, device=x.device, dtype=torch.float64)
+    b = b.detach().contiguous().view(-1).float()
+    r = residual.detach().contiguous().float() if residual is not None else None
+    call("cnrma_bn_train_forward_f32", ptr(x), n, C, ptr(w), ptr(b), float(eps), ptr(r), act, float(momentum),
+         ptr(running_mean), ptr(running_var), ptr(batches), ptr(out), ptr(ws), stream())
+    st.eps, st.ws, st.has_res, st.act = float(eps), ws, residual is not None, act
+    return out
+
+
+def _bn_train_bwd(st, grad_out, x, y, w):
+    """(dx, dw, db, dres) by cnrma_bn_train_backward_f32; x, w as in _bn_train_fwd, y = its saved output (None without an
+    activation: the residual branch then takes the incoming gradient as it is)"""
+    n, C = x.shape
+    g = grad_out.contiguous().float()
+    dx = torch.empty_like(x)
+    dres = torch.empty_like(x) if st.has_res and y is not None else None
+    dw = torch.empty(C, dtype=torch.float32, device=x.device)
+    db = torch.empty(C, dtype=torch.float32, device=x.device)
+    ws2 = _lib.scratch("cnrma_instnorm_workspace_bytes", C, device=x.device, dtype=torch.float64)
+    call("cnrma_bn_train_backward_f32", ptr(g), ptr(x), ptr(y), st.act, n, C, ptr(st.ws), ptr(w), st.eps, ptr(dx), ptr(dres),
+         ptr(dw), ptr(db), ptr(ws2), stream())
+    if st.has_res and dres is None:
+        dres = g
+    return dx, dw, db, dres
+
+
+def _bn_hip_takes(C, bn, *float_tensors):
+    """the library's training BatchNorm takes C channels of `bn`: C <= 256, C % 4 == 0, affine, running statistics tracked
+    with a fixed momentum, and every given operand (None: absent) is fp32"""
+    return (BN_TRAIN_HIP and C <= 256 and C % 4 == 0 and bn.affine and bn.track_running_stats and bn.momentum is not None
+            and all(t is None or t.dtype == torch.float32 for t in float_tensors))
 
 
 def batch_norm_train(F, bn, relu=False, residual=None):
     """training-mode forward of an nn.BatchNorm1d `bn` on F [n, C], optionally fused with a residual add and an activation
-    (relu: False / True = "relu" / "elu"): act( bn(F) [+ residual] ), running statistics updated.  Through the HIP kernels where they take the shape (C <= 256,
-    C % 4 == 0, affine, fixed momentum); torch otherwise"""
+    (relu: False / True = "relu" / "elu"): act( bn(F) [+ residual] ), running statistics updated.  Through the HIP kernels where
+    they take the shape (_bn_hip_takes) and there are two rows or more; torch otherwise"""
     n, C = F.shape
-    if (not BN_TRAIN_HIP or not F.is_cuda or n < 2 or C > 256 or C % 4 or not bn.affine or not bn.track_running_stats
-            or bn.momentum is None or F.dtype != torch.float32 or (residual is not None and residual.dtype != torch.float32)):
+    if not F.is_cuda or n < 2 or not _bn_hip_takes(C, bn, F, residual):
         out = bn(F)
         if residual is not None:
             out = out + residual
-        return torch.nn.functional.elu(out) if relu == "elu" else (torch.relu(out) if relu else out)
+        return _act_torch(out, relu)
     return _BatchNormTrainFn.apply(F, bn.weight, bn.bias, residual, bn.eps, relu, bn.momentum, bn.running_mean, bn.running_var,
                                    bn.num_batches_tracked)
 
@@ -1450,7 +1427,7 @@ def union_add(a, b):
     out_c = torch.empty((na + nb, 4), dtype=torch.int32, device=dev)
     out_f = torch.empty((na + nb, C), dtype=torch.float32, device=dev)
     n_out = torch.empty(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(_lib.load().cnrma_union_workspace_bytes(nb), dtype=torch.uint8, device=dev)
+    ws = _lib.scratch("cnrma_union_workspace_bytes", nb, device=dev)
     nbatch = max(a.cs.n_batch, b.cs.n_batch)
     out_cap = max(na, P.current().next_cap(na + nb)) if P.static() else na + nb
     call("cnrma_sparse_union_add_f32", ptr(a.C), ptr(a.F.contiguous()), na, ptr(a.cs.n_dev), ptr(b.C), ptr(b.F.contiguous()),
@@ -1579,7 +1556,7 @@ def topk_mask(scores, k, n_dev=None):
     mask = torch.empty(n, dtype=torch.uint8, device=scores.device)
     if n_dev is None:
         n_dev = _n_word(scores.device, n)
-    ws = torch.empty(_lib.load().cnrma_sample_workspace_bytes(), dtype=torch.uint8, device=scores.device)
+    ws = _lib.scratch("cnrma_sample_workspace_bytes", device=scores.device)
     call("cnrma_topk_mask_f32", ptr(scores), ptr(n_dev), n, int(k), ptr(mask), ptr(ws), stream())
     return mask
 
@@ -1611,14 +1588,14 @@ def topk_indices(scores, k, n_dev=None):
     if 0 < k <= 1024 and n > 0:          # one select + one single-workgroup sort of the k survivors (2 + 8 launches, no torch ops)
         _lib.require_gpu()
         out = torch.empty(k, dtype=torch.int64, device=scores.device)
-        ws = torch.empty(_lib.load().cnrma_sample_workspace_bytes(), dtype=torch.uint8, device=scores.device)
+        ws = _lib.scratch("cnrma_sample_workspace_bytes", device=scores.device)
         call("cnrma_topk_indices_f32", ptr(scores), ptr(n_dev if n_dev is not None else _n_word(scores.device, n)), n, int(k),
              ptr(out), ptr(ws), stream())
         return out
     mask = topk_mask(scores, k, n_dev)
     sel = torch.empty(n, dtype=torch.int32, device=scores.device)
     n_sel = torch.empty(1, dtype=torch.int32, device=scores.device)
-    ws = torch.empty(_lib.load().cnrma_scan_workspace_bytes(n), dtype=torch.uint8, device=scores.device)
+    ws = _lib.scratch("cnrma_scan_workspace_bytes", n, device=scores.device)
     call("cnrma_mask_to_index", ptr(mask), ptr(sel), ptr(n_sel), n, ptr(ws), stream())     # sel[row] = output slot or -1
     rows = torch.zeros(k + 1, dtype=torch.int64, device=scores.device)                      # slot -> row (slot k: dump)
     rows.scatter_(0, torch.where(sel >= 0, sel, torch.full_like(sel, k)).long().clamp_(max=k),
@@ -1737,13 +1714,12 @@ def assign_targets(points, level_cap, gt, limit, topk, level_live=None, cs=None)
     pos_box = torch.empty(p_cap, dtype=torch.int32, device=dev)
     pos_ctr = torch.empty(p_cap, dtype=torch.float32, device=dev)
     n_pos = torch.empty(1, dtype=torch.int32, device=dev)
-    nbytes = _lib.load().cnrma_fcaf3d_assign_workspace_bytes(n_cap, len(caps), m_cap)
-    if nbytes == 0:
+    ws = _lib.scratch("cnrma_fcaf3d_assign_workspace_bytes", n_cap, len(caps), m_cap, device=dev)
+    if ws.numel() == 0:
         raise ValueError(f"assign_targets: unsupported sizes (n_cap {n_cap}, {len(caps)} levels, m_cap {m_cap} of at most 1024)")
-    ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
     call("cnrma_fcaf3d_assign_f32", ptr(points), ctypes.addressof(host_caps), len(caps), ptr(level_live), ptr(boxes), ptr(cs),
          ptr(volume), ptr(gt.labels), int(gt.labels.dtype == torch.int64), m_cap, ptr(gt.n_live), int(limit), int(topk),
-         ptr(ws), nbytes, ptr(labels), ptr(pos_row), ptr(pos_box), ptr(pos_ctr), ptr(n_pos), stream())
+         ptr(ws), ws.numel(), ptr(labels), ptr(pos_row), ptr(pos_box), ptr(pos_ctr), ptr(n_pos), stream())
     return labels, pos_row, pos_box, pos_ctr, n_pos
 
 
@@ -1758,10 +1734,9 @@ class _FocalLossSum(torch.autograd.Function):
         _, host_caps = _level_array(caps)
         out = torch.empty((), dtype=torch.float32, device=x.device)
         grad = torch.empty_like(x)
-        nbytes = _lib.load().cnrma_fcaf3d_focal_loss_workspace_bytes(n_cap, n_cls)
-        ws = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch("cnrma_fcaf3d_focal_loss_workspace_bytes", n_cap, n_cls, device=x.device)      # >= 8 bytes for n_cls >= 1
         call("cnrma_fcaf3d_focal_loss_f32", ptr(x), ptr(labels), ctypes.addressof(host_caps), len(caps), ptr(level_live), n_cls,
-             float(gamma), float(alpha), ptr(ws), nbytes, ptr(out), ptr(grad), stream())
+             float(gamma), float(alpha), ptr(ws), ws.numel(), ptr(out), ptr(grad), stream())
         ctx.save_for_backward(grad)
         ctx.dtype = cls_score.dtype
         return out
@@ -1793,10 +1768,9 @@ class _PositiveLossSums(torch.autograd.Function):
         p_cap, cols = b.shape
         sums = torch.empty(3, dtype=torch.float32, device=x.device)
         g_logit, g_box = torch.empty_like(x), torch.empty_like(b)
-        nbytes = _lib.load().cnrma_fcaf3d_positive_losses_workspace_bytes(p_cap)
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=x.device)
+        ws = _lib.scratch("cnrma_fcaf3d_positive_losses_workspace_bytes", p_cap, device=x.device)
         call("cnrma_fcaf3d_positive_losses_f32", ptr(x), ptr(b), cols, int(bool(rotated)), ptr(gt_boxes), gt_boxes.shape[0],
-             ptr(pos_box), ptr(pos_ctr), ptr(n_pos), p_cap, ptr(ws), nbytes, ptr(sums), ptr(g_logit), ptr(g_box), stream())
+             ptr(pos_box), ptr(pos_ctr), ptr(n_pos), p_cap, ptr(ws), ws.numel(), ptr(sums), ptr(g_logit), ptr(g_box), stream())
         ctx.save_for_backward(g_logit, g_box)
         ctx.logit_shape, ctx.dtypes = logit.shape, (logit.dtype, pred_boxes.dtype)
         return sums
