@@ -148,6 +148,9 @@ SIGNATURES = {
     "cnrma_cloud_score_f64": (c_int, [P, L, P, D, P, c_size_t, P, P]),
     "cnrma_tsdf_fuse_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, I, F, F, F, P, P, P, P, P]),
     "cnrma_tsdf_fuse_finish_f32": (c_int, [P, P, P, L, P, P, P]),
+    "cnrma_tsdf_resample_f32": (c_int, [P, I, I, I, P, F, P, P, I, I, I, P, P]),
+    "cnrma_tsdf_resample_attr_f32": (c_int, [P, I, I, I, I, P, F, P, P, I, I, I, P, P]),
+    "cnrma_tsdf_resample_attr_i64": (c_int, [P, I, I, I, I, P, F, P, P, I, I, I, L, I, P, P]),
 }
 
 # libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)

@@ -931,6 +931,48 @@ int cnrma_tsdf_fuse_f32(const float* proj, const float* depth, const float* colo
 int cnrma_tsdf_fuse_finish_f32(const float* tsdf, const float* weight, const float* color_vol, int64_t n, float* tsdf_out,
                                float* color_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------------------
+ * a17  TSDF resampling: a volume and its attribute volumes under a rigid transform   replaces TSDF.transform
+ *      (projects/mvsdetection/datasets/tsdf.py:112-180; with attribute volumes data_prepare/scannet/tsdf.py:266-349: an index grid, a
+ *      matrix product, two grid_sample passes and two masked overwrites).  The pinned behaviour is that transform on the CPU, bit for
+ *      bit, for every voxel; its matrix product is pinned as the un-fused sum below (the order a BLAS takes is not torch's to choose).
+ * src [X][Y][Z] and dst [nx][ny][nz] are DEVICE, row-major (z fastest), each of fewer than 2^31 voxels; X, Y, Z >= 2.
+ * src_origin3_dev [3], transform12_dev [3][4] (new world -> old world), dst_origin3_dev [3]: DEVICE.  One lane per output voxel.
+ * All arithmetic is fp32, nothing fused, every division an IEEE division.  For output index (i0, i1, i2) and axis a:
+ *     w_a = (float)i_a * voxel_size + dst_origin[a]                                     (product rounded, then the sum)
+ *     p_r = ((T[r][0] * w_0 + T[r][1] * w_1) + T[r][2] * w_2) + T[r][3] * 1             (un-fused, from the left)
+ *     c_a = (p_a - src_origin[a]) / voxel_size
+ *     n_a = 2 * c_a / (float)(dim_a - 1) - 1                                            (dim = X, Y, Z)
+ *     border = any_a(|n_a| >= 1)                                                        (a NaN compares false)
+ *     s_a = ((n_a + 1) * (float)dim_a - 1) / 2          (grid_sample's align_corners=False reading of a grid normalised the
+ *                                                        align_corners=True way: kept as the reference has it)
+ *     nearest:   index rint(s_a), ties to even; the value is 0 when any index is outside [0, dim_a).  That test stays although
+ *                border is tested as well: border voxels of an integer volume without fill are sampled, and s_a may equal
+ *                dim_a - 0.5, whose rint is dim_a for an even dim_a.
+ *     trilinear: f_a = floor(s_a), lower weight (f_a + 1) - s_a, upper weight s_a - f_a, corner weight (w_z * w_y) * w_x;
+ *                acc = +0, then acc += v * weight over the corners INSIDE the volume only, z offset fastest, then y, then x
+ *                (ATen's tnw, tne, tsw, tse, bnw, bne, bsw, bse).
+ * cnrma_tsdf_resample_f32: near = nearest, lin = trilinear; dst = border ? 1 : (|near| < 1 ? lin : near).  A wave whose voxels are
+ *   all on the border stores +1 and reads nothing of src; a wave with no lane in the band |near| < 1 skips the corner gathers.
+ * cnrma_tsdf_resample_attr_f32: C channels, src [C][X][Y][Z] -> dst [C][nx][ny][nz], trilinear; no band rule, no border fill
+ *   (the reference's rule for float attribute volumes such as 'color').
+ * cnrma_tsdf_resample_attr_i64: C channels of int64, nearest; with fill_border != 0 border voxels get border_fill instead (the
+ *   reference fills 'semseg' with -1 and leaves 'instance' as sampled, data_prepare/scannet/tsdf.py:327-344).  Labels are gathered
+ *   as integers; the reference takes them through fp32, which is the same for |label| < 2^24.
+ * Each returns -22, before any launch, for a source dimension below 2, a negative size, a volume of 2^31 voxels or more, or a NULL
+ *   pointer; an output without voxels (or C == 0) is a no-op.  No atomics, no reciprocals, no allocation, no synchronisation,
+ *   nothing read back, nothing read from the environment.
+ * ---------------------------------------------------------------------------------------------------------- */
+int cnrma_tsdf_resample_f32(const float* src, int X, int Y, int Z, const float* src_origin3_dev, float voxel_size,
+                            const float* transform12_dev, const float* dst_origin3_dev, int nx, int ny, int nz, float* dst,
+                            void* stream);
+int cnrma_tsdf_resample_attr_f32(const float* src, int C, int X, int Y, int Z, const float* src_origin3_dev, float voxel_size,
+                                 const float* transform12_dev, const float* dst_origin3_dev, int nx, int ny, int nz, float* dst,
+                                 void* stream);
+int cnrma_tsdf_resample_attr_i64(const int64_t* src, int C, int X, int Y, int Z, const float* src_origin3_dev, float voxel_size,
+                                 const float* transform12_dev, const float* dst_origin3_dev, int nx, int ny, int nz,
+                                 int64_t border_fill, int fill_border, int64_t* dst, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

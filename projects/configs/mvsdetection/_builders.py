@@ -85,18 +85,25 @@ def _pipeline(space_transform):
             dict(type='AtlasIntrinsicsPoseToProjection'), dict(type='AtlasCollectData')]
 
 
-def recon_pipelines(voxel_dim_train, voxel_dim_test, pad_xy=1.5, pad_z=.25):
+def _resample(tsdf_resample):
+    """tsdf_resample="device": the ground-truth volumes are resampled by the detector on the GPU instead of by the dataloader
+    worker; the default adds no key to the space transform's config"""
+    return {} if tsdf_resample == "host" else dict(tsdf_resample=tsdf_resample)
+
+
+def recon_pipelines(voxel_dim_train, voxel_dim_test, pad_xy=1.5, pad_z=.25, tsdf_resample="host"):
     train = _pipeline(dict(type='AtlasRandomTransformSpaceRecon', voxel_dim=voxel_dim_train, random_rotation=True,
-                           random_translation=True, paddingXY=pad_xy, paddingZ=pad_z))
-    test = _pipeline(dict(type='AtlasTestTransformSpaceRecon', voxel_dim=voxel_dim_test, origin=[0, 0, 0]))
+                           random_translation=True, paddingXY=pad_xy, paddingZ=pad_z, **_resample(tsdf_resample)))
+    test = _pipeline(dict(type='AtlasTestTransformSpaceRecon', voxel_dim=voxel_dim_test, origin=[0, 0, 0],
+                          **_resample(tsdf_resample)))
     return train, test
 
 
-def detection_pipelines(voxel_dim_train, voxel_dim_test, test_mode):
+def detection_pipelines(voxel_dim_train, voxel_dim_test, test_mode, tsdf_resample="host"):
     train = _pipeline(dict(type='AtlasTransformSpaceDetection', voxel_dim=voxel_dim_train, origin=[0, 0, 0], test=False,
-                           mode='middle'))
+                           mode='middle', **_resample(tsdf_resample)))
     test = _pipeline(dict(type='AtlasTransformSpaceDetection', voxel_dim=voxel_dim_test, origin=[0, 0, 0], test=True,
-                          mode=test_mode))
+                          mode=test_mode, **_resample(tsdf_resample)))
     return train, test
 
 

@@ -9,6 +9,7 @@ from PIL import Image, ImageOps
 
 from ...core.data_container import DataContainer as DC
 from ...registry import PIPELINES
+from ..tsdf import DeferredTSDF
 
 
 @PIPELINES.register_module()
@@ -81,9 +82,13 @@ class AtlasIntrinsicsPoseToProjection(object):
         return data
 
 
-def transform_space(data, transform, voxel_dim, origin):
+def transform_space(data, transform, voxel_dim, origin, resample="host"):
     """change of world frame: poses are mapped by transform^-1, every TSDF level is resampled into a volume of
-    voxel_dim / (its voxel size / the finest voxel size) voxels at `origin`"""
+    voxel_dim / (its voxel size / the finest voxel size) voxels at `origin`.  resample="host": at once, by TSDF.transform;
+    "device": every level becomes a DeferredTSDF, which the detector's data_converter resolves on the GPU (a dataloader worker
+    never touches the device)"""
+    if resample not in ("host", "device"):
+        raise ValueError(f"transform_space: resample must be 'host' or 'device', got {resample!r}")
     inv = torch.inverse(transform)
     for i in range(len(data["extrinsics"])):
         data["extrinsics"][i] = inv @ data["extrinsics"][i]
@@ -91,7 +96,10 @@ def transform_space(data, transform, voxel_dim, origin):
     for vs in sizes:
         key = "tsdf_gt_" + str(vs).zfill(3)
         dim = [int(d / (vs / sizes[0])) for d in voxel_dim]
-        data["tsdf_dict"][key] = data["tsdf_dict"][key].transform(transform, dim, origin)
+        if resample == "device":
+            data["tsdf_dict"][key] = DeferredTSDF(data["tsdf_dict"][key], transform, dim, origin)
+        else:
+            data["tsdf_dict"][key] = data["tsdf_dict"][key].transform(transform, dim, origin)
     return data
 
 
@@ -109,8 +117,8 @@ class AtlasRandomTransformSpaceRecon(object):
     voxel_dim crop inside the (padded) extent of the scene"""
 
     def __init__(self, voxel_dim, random_rotation=True, random_translation=True, paddingXY=1.5, paddingZ=.25,
-                 origin=(0, 0, 0)):
-        self.voxel_dim, self.origin = voxel_dim, list(origin)
+                 origin=(0, 0, 0), tsdf_resample="host"):
+        self.voxel_dim, self.origin, self.tsdf_resample = voxel_dim, list(origin), tsdf_resample
         self.random_rotation, self.random_translation = random_rotation, random_translation
         self.pad_lo = torch.tensor([paddingXY, paddingXY, paddingZ])
         self.pad_hi = torch.tensor([paddingXY, paddingXY, 0.0])
@@ -128,7 +136,7 @@ class AtlasRandomTransformSpaceRecon(object):
         T[:2, :2] = R
         T[:3, 3] = -t
         data["offset"] = -t
-        return transform_space(data, torch.inverse(T), self.voxel_dim, self.origin)
+        return transform_space(data, torch.inverse(T), self.voxel_dim, self.origin, self.tsdf_resample)
 
     def __repr__(self):
         return type(self).__name__
@@ -138,8 +146,8 @@ class AtlasRandomTransformSpaceRecon(object):
 class AtlasTestTransformSpaceRecon(object):
     """test time: the volume starts at the scene's TSDF origin (snapped down by the half-metre the training crops use)"""
 
-    def __init__(self, voxel_dim, origin):
-        self.voxel_dim, self.origin = voxel_dim, origin
+    def __init__(self, voxel_dim, origin, tsdf_resample="host"):
+        self.voxel_dim, self.origin, self.tsdf_resample = voxel_dim, origin, tsdf_resample
 
     def __call__(self, data):
         tsdf = data["tsdf_dict"]["tsdf_gt_004"]
@@ -147,7 +155,7 @@ class AtlasTestTransformSpaceRecon(object):
         T = torch.eye(4)
         T[:3, 3] = offset
         data["offset"] = offset
-        return transform_space(data, T, self.voxel_dim, self.origin)
+        return transform_space(data, T, self.voxel_dim, self.origin, self.tsdf_resample)
 
     def __repr__(self):
         return type(self).__name__

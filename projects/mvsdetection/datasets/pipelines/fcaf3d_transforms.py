@@ -98,9 +98,10 @@ class AtlasTransformSpaceDetection(object):
     them and records `offset` = -translation, which the detector adds back to every aggregated point
     (ray_marching.py:364), so the saved boxes are in the original world frame."""
 
-    def __init__(self, voxel_dim, origin=(0, 0, 0), test=False, mode="middle"):
+    def __init__(self, voxel_dim, origin=(0, 0, 0), test=False, mode="middle", tsdf_resample="host"):
         assert mode in ("middle", "origin")
         self.voxel_dim, self.origin, self.test, self.mode = voxel_dim, list(origin), test, mode
+        self.tsdf_resample = tsdf_resample
 
     def __call__(self, data):
         from .atlas_transforms import transform_space
@@ -120,7 +121,7 @@ class AtlasTransformSpaceDetection(object):
             data["gt_bboxes_3d"].translate(t)
         T = torch.eye(4)
         T[:3, 3] = t
-        return transform_space(data, torch.inverse(T), self.voxel_dim, self.origin)
+        return transform_space(data, torch.inverse(T), self.voxel_dim, self.origin, self.tsdf_resample)
 
     def __repr__(self):
         return type(self).__name__

@@ -67,6 +67,13 @@ class TSDF:
         from cnrma_amd import mesh
         return mesh.marching_cubes(self.tsdf_vol, self.voxel_size, self.origin)
 
+    def transform_device(self, transform=None, voxel_dim=None, origin=None):
+        """transform() as one gather kernel per volume on the GPU (cnrma_amd.resample.resample_tsdf: the arithmetic of transform
+        on the CPU bit for bit, attribute volumes carried along, always three output axes).  Raises the library's CnrmaError
+        when it is not built or the volume is not on a GPU."""
+        from cnrma_amd import resample
+        return resample.resample_tsdf(self, transform, voxel_dim, origin)
+
     def transform(self, transform=None, voxel_dim=None, origin=None, align_corners=False):
         """resample under the rigid map `transform` (new world -> old world, 4x4 or 3x4) into a volume of `voxel_dim`
         voxels whose voxel (0,0,0) sits at `origin`: nearest sample everywhere, trilinear where the nearest sample is
@@ -90,3 +97,40 @@ class TSDF:
         near[band] = lin[band]
         near[(grid.abs() >= 1).squeeze(0).any(3)] = 1
         return TSDF(self.voxel_size, origin, near)
+
+
+class DeferredTSDF:
+    """A resampling that has been drawn but not yet computed: what transform_space(..., resample="device") puts into `tsdf_dict`
+    in place of source.transform(transform, voxel_dim, origin).  The detector's data_converter resolves it on the GPU
+    (resolve()); `voxel_size` and the new `origin` are known at once, and any other reader gets the host result, computed on first
+    use: `tsdf_vol`, and through host() every other attribute and method of the TSDF that transform() returns today."""
+
+    def __init__(self, source, transform, voxel_dim, origin):
+        self.source, self.transform_matrix, self.voxel_dim = source, transform, list(voxel_dim)
+        self.new_origin = origin
+        self.voxel_size = source.voxel_size
+        self.origin = (source.origin if origin is None else
+                       torch.tensor(origin, dtype=torch.float, device=source.tsdf_vol.device).view(1, 3))
+        self._host = None
+
+    def host(self):
+        """the TSDF of the host path (source.transform), computed once"""
+        if self._host is None:
+            self._host = self.source.transform(self.transform_matrix, self.voxel_dim, self.new_origin)
+        return self._host
+
+    @property
+    def tsdf_vol(self):
+        return self.host().tsdf_vol
+
+    def resolve(self, device):
+        """the resampled TSDF (volume only, as transform() returns it) computed on `device` by cnrma_amd.resample; the source
+        is left where it is"""
+        from cnrma_amd import resample
+        src = TSDF(self.voxel_size, self.source.origin, self.source.tsdf_vol.to(device))      # the origin crosses with the transform
+        return resample.resample_tsdf(src, self.transform_matrix, self.voxel_dim, self.new_origin)
+
+    def __getattr__(self, name):                                   # only reached for names this class does not define
+        if name.startswith("_") or "source" not in self.__dict__:
+            raise AttributeError(name)
+        return getattr(self.host(), name)

@@ -11,7 +11,7 @@ from torch import nn
 
 from cnrma_amd import rma
 
-from ..datasets.tsdf import TSDF
+from ..datasets.tsdf import TSDF, DeferredTSDF
 from ..registry import build_backbone, build_head
 
 
@@ -164,8 +164,9 @@ class MultiViewBase(nn.Module):
         if "tsdf_dict" in data:
             names = list(data["tsdf_dict"][0].keys())
             dev = data["projection"].device
-            data["tsdf_list"] = {n: torch.stack([d[n].tsdf_vol.unsqueeze(0) for d in data["tsdf_dict"]], 0).to(dev)
-                                 for n in names}
+            # a DeferredTSDF (pipelines built with tsdf_resample="device") is resampled here, on the detector's device
+            vols = [{n: d[n].resolve(dev) if isinstance(d[n], DeferredTSDF) else d[n] for n in names} for d in data["tsdf_dict"]]
+            data["tsdf_list"] = {n: torch.stack([d[n].tsdf_vol.unsqueeze(0) for d in vols], 0).to(dev) for n in names}
             data.pop("tsdf_dict")
         data.pop("axis_align_matrix", None)
         return data
