@@ -1,6 +1,6 @@
-"""ctypes binding of csrc/libcnrma_hip.so (the C-ABI declared in include/cnrma.h).
-
-The product path has NO fallback: if the library is missing or a symbol is absent this module raises.
+"""ctypes binding of csrc/libcnrma_hip.so.  The binding IS the C-ABI's header: the signatures and the integer constants are read
+from include/cnrma.h once, at import (_read_header); nothing here restates a prototype or a #define.
+The product path has NO fallback: if the header or the library is missing or a symbol is absent this module raises.
 
 Two libraries are built from the same sources: libcnrma_hip.so (the product: shipped kernels only, no cnrma_debug_* entry point,
 no tuning state) and libcnrma_hip_exp.so (-DCNRMA_EXPERIMENTS: + the measured-and-rejected kernel forms behind
@@ -9,165 +9,65 @@ sparse.conv_tuning(...) / rma.dense_tuning(...) with arguments, i.e. by scripts/
 process's calls through the second until `experiments(False)`.
 """
 import ctypes
-import threading
 import os
-from ctypes import c_double, c_float, c_int, c_int64, c_size_t, c_void_p
+import re
+import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip.so")
 EXP_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip_exp.so")
-
-P, I, L, F, D = c_void_p, c_int, c_int64, c_float, c_double
-
-# name -> (restype, argtypes); mirrors include/cnrma.h one to one
-SIGNATURES = {
-    "cnrma_fill_bytes_u8": (c_int, [P, I, c_size_t, P]),
-    "cnrma_abi_version": (c_int, []),
-    "cnrma_range_violations_i32": (c_int, [P, P, P, I, P, P]),
-    "cnrma_nchw_to_nhwc_f32": (c_int, [P, P, I, I, I, I, P]),
-    "cnrma_backproject_accum_f32": (c_int, [P, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
-    "cnrma_backproject_accum_ref_f32": (c_int, [P, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
-    "cnrma_backproject_accum_h16": (c_int, [P, P, I, P, I, I, I, I, I, I, I, F, F, F, F, P, P, P, L, P]),
-    "cnrma_nchw_to_nhwc_b16": (c_int, [P, P, I, I, I, I, P]),
-    "cnrma_backproject_backward_f32": (c_int, [P, P, P, I, I, I, I, I, I, I, F, F, F, F, P, P]),
-    "cnrma_backproject_index_f32": (c_int, [P, I, I, I, I, I, F, F, F, F, P, P, P, P]),
-    "cnrma_ray_params_f32": (c_int, [P, I, I, I, P, P, P]),
-    "cnrma_rma_neus_count_f32": (c_int, [P, P, I, I, I, I, I, I, F, F, F, F, I, F, F, P, P, P]),
-    "cnrma_rma_neus_emit_f32": (c_int, [P, P, P, I, I, I, I, I, I, I, F, F, F, F, I, F, F, P, P, P, F, F, F,
-                                        P, I, P, I, P, I, P, P]),
-    "cnrma_rma_neus_rows_backward_f32": (c_int, [P, I, I, I, I, I, P, P, I, P, P, P, P]),
-    "cnrma_rma_sigmoid_table_f32": (c_int, [P, L, P, P]),
-    "cnrma_rma_skip_table_bytes": (c_size_t, [I, I, I]),
-    "cnrma_rma_march_tables_f32": (c_int, [P, I, I, I, P, P, P]),
-    "cnrma_rma_neus_march_f32": (c_int, [P, P, P, I, I, I, I, I, I, F, F, F, F, I, F, F, P, P, P, I, P, P, P]),
-    "cnrma_nchw_to_nhwc_march_f32": (c_int, [P, P, I, P, P, P, I, I, I, I, I, I, F, F, F, F, I, F, F, P, P, P, I, P, P, P]),
-    "cnrma_rma_neus_emit_rows_f32": (c_int, [P, P, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
-    "cnrma_rma_neus_emit_rows_ref_f32": (c_int, [P, P, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
-    "cnrma_rma_neus_emit_rows_h16": (c_int, [P, P, P, I, I, I, I, I, I, F, P, L, P, P, I, P, L, P, P, F, F, F, P, I, P, I, P, I, P, P]),
-    "cnrma_sample_workspace_bytes": (c_size_t, []),
-    "cnrma_sample_mask": (c_int, [P, L, I, ctypes.c_uint32, P, P, P, P]),
-    "cnrma_topk_mask_f32": (c_int, [P, P, L, I, P, P, P]),
-    "cnrma_topk_indices_f32": (c_int, [P, P, L, I, P, P, P]),
-    "cnrma_rma_select_records": (c_int, [P, L, P, I, P, L, I, ctypes.c_uint32, P, P, P, P, P, L, P, P, P]),
-    "cnrma_rma_depth_count_f32": (c_int, [P, P, I, I, I, I, I, I, F, F, F, F, I, F, I, P, P, P]),
-    "cnrma_rma_depth_emit_f32": (c_int, [P, P, P, I, I, I, I, I, I, I, F, F, F, F, I, F, I, P, P, P, F, F, F,
-                                         P, I, P, I, P, I, L, L, P]),
-    "cnrma_rma_drop_single_sample_views": (c_int, [P, P, I, L, P]),
-    "cnrma_rma_mean_weight": (c_int, [P, P, P, P]),
-    "cnrma_scan_workspace_bytes": (c_size_t, [L]),
-    "cnrma_exclusive_scan_i32": (c_int, [P, P, L, P, P]),
-    "cnrma_sum_f64": (c_int, [P, P, L, P, P]),
-    "cnrma_mask_to_index": (c_int, [P, P, P, L, P, P]),
-    "cnrma_select_rows_f32": (c_int, [P, L, I, P, F, F, F, P, P, P]),
-    "cnrma_voxelize_workspace_bytes": (c_size_t, [L]),
-    "cnrma_voxelize_f32": (c_int, [P, P, L, P, I, F, I, I, P, P, L, P, P, P, L, P, P, P]),
-    "cnrma_sparse_build_map": (c_int, [P, L, P, P, P, L, I, P]),
-    "cnrma_sparse_stride_coords": (c_int, [P, L, P, I, P, P, L, P, L, P, P, P]),
-    "cnrma_sparse_stride_coords_sorted": (c_int, [P, L, P, I, P, L, P, P, P]),
-    "cnrma_sparse_kernel_map": (c_int, [P, L, P, P, P, L, P, I, P, P]),
-    "cnrma_sparse_kernel_map_symmetric": (c_int, [P, L, P, P, P, L, P, I, P, I, P]),
-    "cnrma_sparse_kernel_map_children": (c_int, [P, L, P, P, P]),
-    "cnrma_sparse_kernel_map_strided": (c_int, [P, L, P, I, I, P, P, L, P, L, I, P]),
-    "cnrma_sparse_conv_workspace_bytes": (c_size_t, [L, I, I]),
-    "cnrma_sparse_conv_plan": (c_int, [L, I, I, I, I, I, c_size_t, P]),
-    "cnrma_sparse_conv_f32": (c_int, [P, I, P, I, P, I, P, P, P, I, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_conv_weight_bytes": (c_size_t, [I, I, I]),
-    "cnrma_sparse_conv_prepare_weights": (c_int, [P, I, I, I, P, P]),
-    "cnrma_sparse_split_features": (c_int, [P, L, P, I, P, P]),
-    "cnrma_sparse_conv_bf16x6": (c_int, [P, P, L, I, P, I, P, I, P, P, P, I, P, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_convtr_gen_bf16x6": (c_int, [P, P, P, L, P, I, I, P, I, P, P, I, P, P, P, P]),
-    "cnrma_amax_bytes": (c_size_t, []),
-    "cnrma_absmax_f32": (c_int, [P, L, P, I, P, P]),
-    "cnrma_rma_emit_features_f32": (c_int, [P, P, I, P, L, P, P, P, I, P, P]),
-    "cnrma_rma_emit_features_h16": (c_int, [P, P, I, I, P, L, P, P, P, I, P, P]),
-    "cnrma_sparse_conv_f16_weight_bytes": (c_size_t, [I, I, I]),
-    "cnrma_sparse_conv_prepare_weights_f16": (c_int, [P, I, I, I, P, P]),
-    "cnrma_sparse_conv_f16x3": (c_int, [P, P, I, P, I, P, I, P, P, P, I, P, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_tile_union_bytes": (c_size_t, [L]),
-    "cnrma_sparse_tile_union_build": (c_int, [P, L, P, I, P, P]),
-    "cnrma_sparse_conv_prepare_weights_f16_frag": (c_int, [P, I, I, I, P, P]),
-    "cnrma_sparse_conv_f32_frag_weight_bytes": (c_size_t, [I, I, I]),
-    "cnrma_sparse_conv_prepare_weights_f32_frag": (c_int, [P, I, I, I, P, P]),
-    "cnrma_sparse_conv_go_f32": (c_int, [P, I, P, P, I, P, P, P, I, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_conv_go_plan": (c_int, [L, I, I, c_size_t, I, P]),
-    "cnrma_sparse_conv_go_f16x3": (c_int, [P, P, I, P, P, I, P, P, P, I, P, P, L, P, P, c_size_t, P, P]),
-    "cnrma_sparse_conv_pairs_workspace_bytes": (c_size_t, [L, I, I, L]),
-    "cnrma_sparse_conv_pairs_f32": (c_int, [P, I, P, I, P, I, P, P, P, I, P, L, P, L, P, c_size_t, P]),
-    "cnrma_sparse_conv_pairs_f16x3": (c_int, [P, P, I, P, I, P, I, P, P, P, I, P, P, L, P, L, P, c_size_t, P]),
-    "cnrma_sparse_conv_bf16_weight_bytes": (c_size_t, [I, I, I]),
-    "cnrma_sparse_conv_prepare_weights_bf16": (c_int, [P, I, I, I, P, P]),
-    "cnrma_sparse_conv_prepare_weights_bf16_t": (c_int, [P, I, I, I, I, P, P]),
-    "cnrma_sparse_conv_bf16": (c_int, [P, I, P, I, P, I, P, P, P, I, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_convtr_gen_f16x3": (c_int, [P, P, P, L, P, I, I, P, I, P, P, I, P, P, P, P]),
-    "cnrma_sparse_kernel_map_transpose": (c_int, [P, L, P, I, L, P, P]),
-    "cnrma_sparse_conv_wgrad_chunks": (c_int, [L, I]),
-    "cnrma_sparse_conv_wgrad_f32": (c_int, [P, I, P, I, P, I, L, P, I, P, P]),
-    "cnrma_sparse_conv_wgrad_bf16": (c_int, [P, I, P, I, P, I, L, P, I, P, P]),
-    "cnrma_sparse_conv_wgrad_go_bf16": (c_int, [P, I, P, P, I, L, P, I, P, P]),
-    "cnrma_sparse_conv_bf16_frag_weight_bytes": (c_size_t, [I, I, I]),
-    "cnrma_sparse_conv_prepare_weights_bf16_frag": (c_int, [P, I, I, I, I, I, P, P]),
-    "cnrma_sparse_conv_prepare_weights_bf16_frag_pair": (c_int, [P, I, I, I, I, P, P, P]),
-    "cnrma_sparse_conv_go_bf16": (c_int, [P, I, P, P, I, P, L, P, P, c_size_t, P]),
-    "cnrma_sparse_convtr_gen_f32": (c_int, [P, P, L, P, I, I, P, I, P, P, I, P, P, P]),
-    "cnrma_sparse_maxpool_f32": (c_int, [P, I, P, I, P, L, P, P]),
-    "cnrma_instnorm_workspace_bytes": (c_size_t, [I]),
-    "cnrma_sparse_instnorm_f32": (c_int, [P, L, P, P, I, P, P, F, I, P, P, P]),
-    "cnrma_sparse_instnorm_maxpool_f32": (c_int, [P, I, P, P, P, F, I, P, I, P, L, P, P, P]),
-    "cnrma_bn_backward_f32": (c_int, [P, P, L, I, P, P, F, P, P, P, P, P]),
-    "cnrma_bn_train_forward_f32": (c_int, [P, L, I, P, P, F, P, I, F, P, P, P, P, P, P]),
-    "cnrma_bn_train_backward_f32": (c_int, [P, P, P, I, L, I, P, P, F, P, P, P, P, P, P]),
-    "cnrma_union_workspace_bytes": (c_size_t, [L]),
-    "cnrma_sparse_union_add_f32": (c_int, [P, P, L, P, P, P, L, P, I, P, P, L, P, P, L, P, P, P]),
-    "cnrma_sparse_interp_f32": (c_int, [P, L, P, P, P, P, L, I, P, P]),
-    "cnrma_sparse_prune_f32": (c_int, [P, P, L, P, I, P, P, P, P]),
-    "cnrma_rowmax_f32": (c_int, [P, L, P, I, P, P]),
-    "cnrma_fcaf3d_decode_f32": (c_int, [P, P, I, L, I, P, P]),
-    "cnrma_fcaf3d_head_post_f32": (c_int, [P, I, P, L, I, I, P, F, P, P, P, P, P, P]),
-    "cnrma_fcaf3d_max_score_f32": (c_int, [P, P, L, I, P, P]),
-    "cnrma_fcaf3d_select_decode_f32": (c_int, [P, L, P, P, P, P, I, I, I, P, P, P]),
-    "cnrma_nms_mask_f32": (c_int, [P, I, F, I, P, P]),
-    "cnrma_box_iou_f32": (c_int, [P, I, P, I, I, I, P, P]),
-    "cnrma_fcaf3d_scores_f32": (c_int, [P, P, L, I, P, P, P]),
-    "cnrma_nms_classes_workspace_bytes": (c_size_t, [I, I]),
-    "cnrma_nms_classes_f32": (c_int, [P, I, P, I, I, P, I, P, F, F, P, c_size_t, P, P, P, I, P, P]),
-    "cnrma_fcaf3d_assign_workspace_bytes": (c_size_t, [L, I, I]),
-    "cnrma_fcaf3d_assign_f32": (c_int, [P, P, I, P, P, P, P, P, I, I, P, I, I, P, c_size_t, P, P, P, P, P, P]),
-    "cnrma_fcaf3d_focal_loss_workspace_bytes": (c_size_t, [L, I]),
-    "cnrma_fcaf3d_focal_loss_f32": (c_int, [P, P, P, I, P, I, F, F, P, c_size_t, P, P, P]),
-    "cnrma_fcaf3d_positive_losses_workspace_bytes": (c_size_t, [I]),
-    "cnrma_fcaf3d_positive_losses_f32": (c_int, [P, P, I, I, P, I, P, P, P, I, P, c_size_t, P, P, P, P]),
-    "cnrma_mesh_workspace_bytes": (c_size_t, [I, I, I]),
-    "cnrma_mesh_count_f32": (c_int, [P, I, I, I, P, c_size_t, P, P]),
-    "cnrma_mesh_emit_f32": (c_int, [P, I, I, I, F, P, P, P, P, L, P, L, P, P]),
-    "cnrma_cloud_downsample_workspace_bytes": (c_size_t, [L]),
-    "cnrma_cloud_voxel_downsample_f32": (c_int, [P, L, P, D, P, c_size_t, P, P, L, P, P]),
-    "cnrma_cloud_nn_workspace_bytes": (c_size_t, [L]),
-    "cnrma_cloud_nn_build_f32": (c_int, [P, L, P, D, P, c_size_t, P]),
-    "cnrma_cloud_nn_query_f32": (c_int, [P, L, P, L, P, P, P, P, P]),
-    "cnrma_cloud_score_workspace_bytes": (c_size_t, [L]),
-    "cnrma_cloud_score_f64": (c_int, [P, L, P, D, P, c_size_t, P, P]),
-    "cnrma_tsdf_fuse_f32": (c_int, [P, P, P, P, P, I, I, I, I, I, I, F, F, F, P, P, P, P, P]),
-    "cnrma_tsdf_fuse_finish_f32": (c_int, [P, P, P, L, P, P, P]),
-    "cnrma_tsdf_resample_f32": (c_int, [P, I, I, I, P, F, P, P, I, I, I, P, P]),
-    "cnrma_tsdf_resample_attr_f32": (c_int, [P, I, I, I, I, P, F, P, P, I, I, I, P, P]),
-    "cnrma_tsdf_resample_attr_i64": (c_int, [P, I, I, I, I, P, F, P, P, I, I, I, L, I, P, P]),
-}
-
-# libcnrma_hip_exp.so exports these on top of SIGNATURES (include/cnrma.h: the prototypes under #ifdef CNRMA_EXPERIMENTS)
-EXPERIMENT_SIGNATURES = {
-    "cnrma_debug_dense_tuning": (c_int, [P, I]),
-    "cnrma_debug_div_by_voxel_size_f32": (c_int, [P, L, F, P, P, P]),
-    "cnrma_debug_conv_tuning": (c_int, [P, I]),
-}
-
-_libs = {}            # False: product library, True: experiments library
-_active = False       # which of the two load() / call() use
-_exp_users = set()    # who asked for the experiments library ("conv", "dense", a test): product again when nobody is left
-ABI_VERSION = 7
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma.h")
+# the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
+_CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+           "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
 
 
 class CnrmaError(RuntimeError):
     pass
+
+
+def _read_header(text):
+    """(prototypes, experiment_prototypes, constants) of include/cnrma.h's text: name -> (restype, [argtypes]) of every
+    `int|size_t cnrma_<name>(...);` outside / inside the `#ifdef CNRMA_EXPERIMENTS ... #endif` blocks, name -> int of every
+    `#define CNRMA_X <int>`.  What it does not know raises: there is no fallback type"""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)       # comments quote prototypes and trail the defines
+    text = text.replace("\\\n", " ")                                # a function-like macro's lines: one #define, not a constant
+    bodies, tables, constants, in_exp = ([], []), ({}, {}), {}, False
+    for line in text.split("\n"):
+        directive = re.match(r"\s*#\s*(\w+)", line)
+        if directive is None:
+            bodies[in_exp].append(line)
+        elif directive.group(1) in ("if", "ifdef", "ifndef", "elif", "else"):
+            if in_exp:                                                # blocks are flat: their first #endif is their own
+                raise CnrmaError(f"cnrma.h: a conditional nested in an #ifdef CNRMA_EXPERIMENTS block: {line.strip()!r}")
+            in_exp = line.split() == ["#ifdef", "CNRMA_EXPERIMENTS"]
+        elif directive.group(1) == "endif":
+            in_exp = False
+        elif m := re.fullmatch(r"\s*#\s*define\s+(CNRMA_\w+)\s+\(?\s*(-?\d+)\s*\)?\s*", line):
+            constants[m.group(1)] = int(m.group(2))
+    for table, body in zip(tables, bodies):
+        for ret, name, params in re.findall(r"(\w+)\s+(cnrma_\w+)\s*\(([^;()]*)\)\s*;", "\n".join(body)):
+            if ret not in ("int", "size_t") or name in tables[0] or name in tables[1]:
+                raise CnrmaError(f"cnrma.h: {name} is declared twice or returns {ret!r}, neither int nor size_t")
+            table[name] = (_CTYPES[ret], [])
+            for param in ([] if params.strip() in ("", "void") else params.split(",")):
+                ctype = "*" if "*" in param else " ".join(w for w in param.split()[:-1] if w != "const")     # [:-1]: its name
+                if ctype not in _CTYPES:
+                    raise CnrmaError(f"cnrma.h: {name}: no ctypes type for the parameter {' '.join(param.split())!r}")
+                table[name][1].append(_CTYPES[ctype])
+    return tables[0], tables[1], constants
+
+
+try:        # name -> (restype, argtypes) in header order: the product surface, and what libcnrma_hip_exp.so exports on top of it
+    with open(HEADER_PATH) as _f:
+        SIGNATURES, EXPERIMENT_SIGNATURES, CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {HEADER_PATH}: {e}") from e
+ABI_VERSION, EINVAL = CONSTANTS["CNRMA_ABI_VERSION"], CONSTANTS["CNRMA_EINVAL"]
+
+_libs = {}            # False: product library, True: experiments library
+_active = False       # which of the two load() / call() use
+_exp_users = set()    # who asked for the experiments library ("conv", "dense", a test): product again when nobody is left
 
 
 def load(experiments=None):
@@ -233,7 +133,7 @@ def stream():
 def call(name, *args):
     rc = getattr(load(), name)(*args)
     if rc != 0:
-        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == -22 else " (-hipError_t)"))
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == EINVAL else " (-hipError_t)"))
     return rc
 
 

@@ -14,7 +14,7 @@ import torch
 from . import _lib
 from ._lib import call, ptr, stream
 
-NONFINITE, VOXEL_TOO_SMALL = 1, 2
+NONFINITE, VOXEL_TOO_SMALL = _lib.CONSTANTS["CNRMA_CLOUD_NONFINITE"], _lib.CONSTANTS["CNRMA_CLOUD_VOXEL_TOO_SMALL"]
 _KEYS = ("dist1", "dist2", "prec", "recal", "fscore")
 
 

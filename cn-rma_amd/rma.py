@@ -50,7 +50,7 @@ def scale_projection(projection, stride):
 # The dense unprojection and the NeuS row emission read them where they lie: both widenings are exact and every sum stays fp32 in
 # view order, so the results are bit-identical to the fp32 kernels on `maps.float()`.  Everything else (depth mode, the legacy
 # cnrma_rma_neus_emit_f32 path, the autograd functions) widens them first, as before.
-ELEM_CODES = {torch.float16: 1, torch.bfloat16: 2}
+ELEM_CODES = {torch.float16: _lib.CONSTANTS["CNRMA_ELEM_F16"], torch.bfloat16: _lib.CONSTANTS["CNRMA_ELEM_BF16"]}
 
 
 def _h16_readable(nhwc):
@@ -134,7 +134,7 @@ _DENSE_WS = {}
 _DENSE_KEYS = ("variant", "slab", "st", "zt", "tt", "zi", "chunk", "persist", "lpv", "pipe", "epi", "lockstep", "lattice", "nt", "own", "stagger", "groups", "ldspad", "zrun")
 
 
-DENSE_WORKSPACE_BYTES = 1024     # CNRMA_DENSE_WORKSPACE_BYTES of include/cnrma.h
+DENSE_WORKSPACE_BYTES = _lib.CONSTANTS["CNRMA_DENSE_WORKSPACE_BYTES"]
 DENSE_MASK_MIN_SWEEPS = 3        # channel sweeps from which on the callers here give the dense kernel room for its view masks.  The
                                  # masked form launches sweep 0 on its own (it records the masks) and the other sweeps behind it.
                                  # Kernel alone, medians of six rounds, masked / every view walked ("per-wave view

@@ -245,7 +245,7 @@ def test_synth_scene_is_deterministic():
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# C-ABI surface: the library loads, exports every symbol of include/cnrma.h, and the ctypes table agrees in arity
+# C-ABI surface: the library loads, exports every symbol of include/cnrma.h, and the ctypes binding agrees in arity and types
 # ---------------------------------------------------------------------------------------------------------------
 def _header_functions(experiments=False):
     """prototypes of include/cnrma.h: the product surface, or (experiments=True) only those under #ifdef CNRMA_EXPERIMENTS"""
@@ -254,11 +254,33 @@ def _header_functions(experiments=False):
     exp = "\n".join(re.findall(r"#ifdef CNRMA_EXPERIMENTS\n(.*?)#endif", src, flags=re.S))
     src = exp if experiments else re.sub(r"#ifdef CNRMA_EXPERIMENTS\n.*?#endif", "", src, flags=re.S)
     out = {}
-    for m in re.finditer(r"\b(?:int|size_t)\s+(cnrma_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
-        args = m.group(2).strip()
-        n = 0 if args in ("", "void") else len(args.split(","))
-        out[m.group(1)] = n
+    for m in re.finditer(r"\b(int|size_t)\s+(cnrma_\w+)\s*\(([^;]*?)\)\s*;", src, flags=re.S):
+        args = m.group(3).strip()
+        out[m.group(2)] = ([] if args in ("", "void") else [_kind(a) for a in args.split(",")], _kind(m.group(1) + " f"))
     return out
+
+
+# name -> (parameters, return value), each a (class, bytes) pair taken from the C text; class: "pointer", "integer" or "floating"
+_C_SCALARS = (("integer", 8, r"(u?int64_t|size_t)"), ("integer", 4, r"(int|u?int32_t)"), ("floating", 4, "float"), ("floating", 8, "double"))
+
+
+def _kind(param):
+    """(class, bytes) of one parameter's C text, name included: what a binding of it has to be, whatever it is called"""
+    if "*" in param:
+        return "pointer", ctypes.sizeof(ctypes.c_void_p)
+    for cls, width, pat in _C_SCALARS:
+        if re.fullmatch(rf"\s*(const\s+)?{pat}(\s+const)?\s+\w+\s*", param):
+            return cls, width
+    raise AssertionError(f"include/cnrma.h: a parameter this test cannot class: {param!r}")
+
+
+def _bound_kind(ctype):
+    """(class, bytes) of a ctypes type as ctypes itself treats it"""
+    if ctype is ctypes.c_void_p:
+        return "pointer", ctypes.sizeof(ctype)
+    code = ctype._type_                      # struct-style type code of a simple ctypes type
+    assert code in "fdbBhHiIlLqQ", ctype
+    return ("floating" if code in "fd" else "integer"), ctypes.sizeof(ctype)
 
 
 def _exported(path):
@@ -290,11 +312,18 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_ctypes_table_matches_header():
+    """two readers of include/cnrma.h written separately -- the product's (_lib._read_header) and this file's regex -- agree on
+    the names, the arity, and for every parameter and return value on its class (pointer / integer / floating) and width: a
+    pointer bound as an int would be cut to 32 bits, a float bound as a double would arrive as garbage"""
     from cnrma_amd import _lib
     for decl, table in ((_header_functions(), _lib.SIGNATURES), (_header_functions(experiments=True), _lib.EXPERIMENT_SIGNATURES)):
         assert set(decl) == set(table), set(decl) ^ set(table)
-        for name, n in decl.items():
-            assert len(table[name][1]) == n, (name, n, len(table[name][1]))
+        for name, (params, returns) in decl.items():
+            restype, argtypes = table[name]
+            assert len(argtypes) == len(params), (name, len(params), len(argtypes))
+            assert _bound_kind(restype) == returns, (name, restype, returns)
+            for i, (ctype, want) in enumerate(zip(argtypes, params)):
+                assert _bound_kind(ctype) == want, (name, i, ctype, want)
     assert not set(_lib.SIGNATURES) & set(_lib.EXPERIMENT_SIGNATURES)
 
 
