@@ -17,6 +17,9 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip.so")
 EXP_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_hip_exp.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma.h")
+# the data-preparation surface: a library and a header of their own (include/cnrma_prep.h), bound the same way
+PREP_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_prep_hip.so")
+PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_prep.h")
 # the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
 _CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
@@ -64,6 +67,14 @@ try:        # name -> (restype, argtypes) in header order: the product surface, 
 except OSError as e:
     raise CnrmaError(f"cannot read the C-ABI header {HEADER_PATH}: {e}") from e
 ABI_VERSION, EINVAL = CONSTANTS["CNRMA_ABI_VERSION"], CONSTANTS["CNRMA_EINVAL"]
+try:
+    with open(PREP_HEADER_PATH) as _f:
+        PREP_SIGNATURES, _prep_exp, PREP_CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {PREP_HEADER_PATH}: {e}") from e
+if _prep_exp:
+    raise CnrmaError(f"cnrma_prep.h declares experiment entry points ({sorted(_prep_exp)}): the preparation library has none")
+PREP_ABI_VERSION = PREP_CONSTANTS["CNRMA_PREP_ABI_VERSION"]
 
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
@@ -91,6 +102,36 @@ def load(experiments=None):
         raise CnrmaError("ABI version mismatch")
     _libs[which] = lib
     return lib
+
+
+_prep_lib = None
+
+
+def load_prep():
+    """libcnrma_prep_hip.so (include/cnrma_prep.h), loaded once; raises loudly when it is not built"""
+    global _prep_lib
+    if _prep_lib is not None:
+        return _prep_lib
+    if not os.path.exists(PREP_LIB_PATH):
+        raise CnrmaError(f"{PREP_LIB_PATH} not found: build it with `python __graft_entry__.py build` "
+                         f"(or `make -C cn-rma_amd/csrc`). There is no CPU fallback for the product path.")
+    lib = ctypes.CDLL(PREP_LIB_PATH)
+    for name, (res, args) in PREP_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    if lib.cnrma_prep_abi_version() != PREP_ABI_VERSION:
+        raise CnrmaError("ABI version mismatch (libcnrma_prep_hip.so)")
+    _prep_lib = lib
+    return lib
+
+
+def call_prep(name, *args):
+    rc = getattr(load_prep(), name)(*args)
+    if rc != 0:
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == PREP_CONSTANTS["CNRMA_PREP_EINVAL"]
+                                                          else " (-hipError_t)"))
+    return rc
 
 
 def experiments(on=True, who="caller"):
