@@ -498,7 +498,7 @@ def rma_view_rows(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_ste
 
 def aggregate_points(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps=300, thr=0.05, mode="neus",
                      select_grids=0, offset=(0.0, 0.0, 0.0), max_points=None, sampler="numpy", mask=None,
-                     reference_quirks=True, seed=None):
+                     reference_quirks=True, seed=None, with_weights=False):
     """Fused aggregate_2d_features_ray_marching (:260-307) + switch_pointcloud test path (:339-407).
 
     Returns (coords [Ms,3], feats [Ms,C], info).  feats = feature * (w / mean(w)) with the mean over ALL M rows of
@@ -509,11 +509,13 @@ def aggregate_points(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_
              "device" -- a uniformly random mask with exactly max_points ones drawn on the GPU (same
                          distribution, different RNG stream; no host RNG on the critical path).
     mask:    optional explicit keep-mask (numpy bool / torch uint8 of length M); overrides `sampler`.
+    with_weights: the emission also writes the weight column of the emitted rows, info["weights"] [Ms] (depth mode and the
+             legacy NeuS emission: what the depth backward scales by).
     """
     st = aggregate_begin(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, mode, select_grids,
                          reference_quirks)
     # the one read-back the reference also has (nonzero(), :781): total row count (+ the record-overflow guard)
-    return aggregate_finish(st, _lib.read_ints(st["readback"]), offset, max_points, sampler, mask, seed)
+    return aggregate_finish(st, _lib.read_ints(st["readback"]), offset, max_points, sampler, mask, seed, with_weights)
 
 
 def aggregate_begin(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps=300, thr=0.05, mode="neus",
@@ -550,7 +552,8 @@ def _row_offsets(m, cnt, wsum, reference_quirks):
     return off, m_total, mean_w
 
 
-def aggregate_finish(st, readback, offset=(0.0, 0.0, 0.0), max_points=None, sampler="numpy", mask=None, seed=None):
+def aggregate_finish(st, readback, offset=(0.0, 0.0, 0.0), max_points=None, sampler="numpy", mask=None, seed=None,
+                     with_weights=False):
     """second half of aggregate_points; readback = st["readback"] as host ints; seed: of the device sampler (None =
     a fresh one per call)"""
     m, single_march, off, kept, mean_w, m_total, cnt = (st[k] for k in ("m", "single_march", "off", "kept", "mean_w",
@@ -586,11 +589,13 @@ def aggregate_finish(st, readback, offset=(0.0, 0.0, 0.0), max_points=None, samp
             Ms = int(n_sel.item())
     coords = torch.empty((Ms, 3), dtype=torch.float32, device=m.dev)
     feats = torch.empty((Ms, m.C), dtype=torch.float32, device=m.dev)
+    weights = torch.empty(Ms, dtype=torch.float32, device=m.dev) if with_weights and not single_march else None
     if single_march:
         m.emit_rows(off, Ms, kept, sel, mean_w, offset, coords.data_ptr(), 3, None, 0, feats.data_ptr(), m.C)
     else:
-        m.emit(off, sel, mean_w, offset, coords.data_ptr(), 3, None, 0, feats.data_ptr(), m.C)
-    info = dict(M=M, M_selected=Ms, mean_w=mean_w, row_offset=off, count=cnt, kept=kept, sel=sel, march=m)
+        m.emit(off, sel, mean_w, offset, coords.data_ptr(), 3, weights.data_ptr() if weights is not None else None, 1,
+               feats.data_ptr(), m.C)
+    info = dict(M=M, M_selected=Ms, mean_w=mean_w, row_offset=off, count=cnt, kept=kept, sel=sel, march=m, weights=weights)
     return coords, feats, info
 
 
@@ -678,24 +683,47 @@ def aggregate_points_backward(info, grad_feats):
     return out
 
 
+def aggregate_depth_points_backward(info, grad_feats):
+    """aggregate_points_backward for depth mode (ray_projection_depth indexes features[b, :, v, u], :947, and scales by
+    w / mean(w), :303-304): every emitted row adds grad_row * w / mean(w) to its ray's pixel.  The ray of a row comes from the
+    per-ray counts and the weight from the emission's weight column (aggregate_points(with_weights=True)), all on the device:
+    no read-back beyond the forward's row count."""
+    m, w, sel, M = info["march"], info["weights"], info["sel"], info["M"]
+    if w is None:
+        raise NotImplementedError("the depth backward needs the weight column of the forward (with_weights=True)")
+    Ms = w.numel()
+    ray = torch.repeat_interleave(torch.arange(m.R, device=m.dev), info["count"].long(), output_size=M)      # ray of every row
+    if sel is not None:                  # sel[row] = place among the emitted rows, < 0: not emitted (those land in a spare slot)
+        place = torch.where(sel < 0, torch.full_like(sel, Ms), sel).long()
+        ray = torch.zeros(Ms + 1, dtype=torch.long, device=m.dev).scatter_(0, place, ray)[:Ms]
+    g = grad_feats.contiguous().float() * (w / info["mean_w"]).view(-1, 1)
+    out = torch.zeros((m.R, m.C), dtype=torch.float32, device=m.dev)
+    return out.index_add_(0, ray, g).view(m.V, m.H, m.W, m.C)
+
+
 class AggregatePoints(torch.autograd.Function):
     """differentiable aggregate_points(): (features NCHW [V,C,H,W], ...) -> (coords [Ms,3], feats [Ms,C]); the gradient
     flows from `feats` to the feature maps (and on into the 2D backbone), like the reference's indexing
-    features[b, :, v, u] (ray_marching.py:793-797)."""
+    features[b, :, v, u] (ray_marching.py:793-797 for NeuS, :947 for mode="depth" with its select_grids)."""
 
     @staticmethod
-    def forward(ctx, features_nchw, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, offset, max_points, sampler, mask):
+    def forward(ctx, features_nchw, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, offset, max_points, sampler, mask,
+                mode="neus", select_grids=0):
         nhwc = to_nhwc(features_nchw.detach())
-        coords, feats, info = aggregate_points(nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, "neus", 0,
-                                               offset, max_points, sampler, mask)
+        coords, feats, info = aggregate_points(nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps, thr, mode,
+                                               select_grids if mode == "depth" else 0, offset, max_points, sampler, mask,
+                                               with_weights=mode == "depth")
         ctx.info = info
         ctx.mark_non_differentiable(coords)
         return coords, feats
 
     @staticmethod
     def backward(ctx, _grad_coords, grad_feats):
-        g = aggregate_points_backward(ctx.info, grad_feats)                 # [V,H,W,C]
-        return (g.permute(0, 3, 1, 2).contiguous(),) + (None,) * 11
+        if ctx.info["march"].mode == "depth":
+            g = aggregate_depth_points_backward(ctx.info, grad_feats)      # [V,H,W,C]
+        else:
+            g = aggregate_points_backward(ctx.info, grad_feats)
+        return (g.permute(0, 3, 1, 2).contiguous(),) + (None,) * 13
 
 
 def aggregate_rows(features_nhwc, proj_inv, tsdf, dims, voxel_size, origin, n_steps=300, thr=0.05, mode="neus",

@@ -226,13 +226,14 @@ class RayMarching(MultiViewBase):
             # into the aggregation -- only the selected rows are emitted (the reference's numpy draw of 500 k out of
             # ~4 M indices alone costs 45 ms of host time per scene); "numpy" keeps the reference's RNG stream
             fused = self.point_sampler == "device" and self.max_points is not None and self.ray_marching_type == "neus"
-            if torch.is_grad_enabled() and features.requires_grad and self.ray_marching_type == "neus":
-                # training: the gradient of the aggregated features flows back into the 2D feature maps (:793-797)
+            if torch.is_grad_enabled() and features.requires_grad and self.ray_marching_type in ("neus", "depth"):
+                # training: the gradient of the aggregated features flows back into the 2D feature maps (:793-797, :947)
                 coords, feats = rma.AggregatePoints.apply(features[:, b], pinv, tsdf[b, 0].detach(), self.voxel_dim,
                                                           self.voxel_size, self.origin.view(-1).tolist(), 300,
                                                           self.neus_threshold, (0.0, 0.0, 0.0),
                                                           self.max_points if fused else None,
-                                                          "device" if fused else "numpy", None)
+                                                          "device" if fused else "numpy", None,
+                                                          self.ray_marching_type, self.depth_points)
                 self.points_detection.append(torch.cat((coords, feats), dim=1))
                 continue
             nhwc = getattr(self, "_nhwc", {}).get((features.data_ptr(), b))      # the dense half's layout pass, if it ran on

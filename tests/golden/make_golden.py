@@ -409,6 +409,120 @@ def check_edge_fixture(name, need_exit=True, need_entry=True, need_depth0=True, 
     return f
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# depth mode (ray_projection_depth, :809-956) at its edges, select_grids = 0..4: first sign changes at step 0 and at
+# N-2 / N-3 (slots sel < 0 and sel >= N are masked, :899-900), rays that enter the grid straight into tsdf <= 0, rays with
+# exactly-zero direction components, a view that misses the grid between views that hit, and voxels of exactly 0.0, -0.0,
+# 1.0 and NaN under the `product <= 0` rule (:876-879)
+# --------------------------------------------------------------------------------------------------------------------
+DEPTH_EDGE_DIMS, DEPTH_EDGE_ORIGIN, DEPTH_EDGE_STEPS, DEPTH_EDGE_STRIDE = (12, 10, 7), (0.1, -0.2, 0.05), 40, 2
+DEPTH_EDGE_HW, DEPTH_EDGE_C = (9, 13), 4
+DEPTH_EDGE_PLANTED = (((4, 4, 3), 0.0), ((5, 5, 3), -0.0), ((5, 4, 4), float("nan")), ((4, 5, 3), 1.0), ((3, 4, 3), -0.0),
+                      ((4, 3, 2), float("nan")), ((6, 4, 2), 0.0), ((3, 5, 4), 1.0), ((5, 4, 2), -0.0), ((4, 3, 4), 0.0))
+
+
+def depth_edges_scene():
+    """views: 0 inside the grid, next to a voxel border; 1 and 3 outside on the diagonal through the outer corner of voxel
+    (0,0,0), 1.5 and 2.5 steps short of t_max = N t_one from it, long focal length; 2 looks away from the grid (no row: an
+    empty view between views that hit); 4 below the grid looking exactly along +z, principal point on a pixel centre"""
+    sys.path.insert(0, os.path.dirname(HERE))
+    from helpers import look_at_projection
+    X, Y, Z = DEPTH_EDGE_DIMS
+    vs, s = 0.04, DEPTH_EDGE_STRIDE
+    org = np.array(DEPTH_EDGE_ORIGIN)
+    t_one = O.step_length(DEPTH_EDGE_DIMS, vs, DEPTH_EDGE_STEPS)
+    g = torch.Generator().manual_seed(31)
+    tsdf = torch.round((torch.rand(X, Y, Z, generator=g) * 2 - 1) * 64) / 64
+    tsdf[tsdf == 0] = 1.0 / 64                                   # the only zeros are the planted ones
+    tsdf = tsdf.clamp(-63.0 / 64, 63.0 / 64)
+    tsdf[:3, :3, :3] = -0.5                                      # what the far cameras' rays enter the grid into
+    for ijk, val in DEPTH_EDGE_PLANTED:
+        tsdf[ijk] = val
+    corner = org - 0.5 * vs
+    diag = np.ones(3) / np.sqrt(3.0)
+    H, W = DEPTH_EDGE_HW
+    cx, cy = s * (W // 2), s * (H // 2)                           # principal point on the centre pixel of the feature map
+    eye_in = org + vs * np.array([5.3, 4.45, 3.4])
+    far = [corner - diag * (DEPTH_EDGE_STEPS - short) * t_one for short in (1.5, 2.5)]
+    eye_axis = org + np.array([5 * vs, 4 * vs, -0.06])
+    projs = [look_at_projection(eye_in, org + vs * np.array([1.0, 2.0, 1.5]), s * 7.0, cx, cy),
+             look_at_projection(far[0], corner, s * 600.0, cx, cy),
+             look_at_projection(org + np.array([-0.3, 0.1, 0.1]), org + np.array([-1.3, 0.0, 0.3]), s * 7.0, cx, cy),
+             look_at_projection(far[1], corner, s * 600.0, cx, cy),
+             look_at_projection(eye_axis, eye_axis + np.array([0.0, 0.0, 1.0]), s * 10.0, cx, cy, up=(0.0, -1.0, 0.0))]
+    sc = edge_scene(DEPTH_EDGE_DIMS, DEPTH_EDGE_ORIGIN, s, DEPTH_EDGE_C, DEPTH_EDGE_HW, projs, tsdf.view(1, 1, X, Y, Z), seed=32)
+    sc["n_steps"] = DEPTH_EDGE_STEPS
+    return sc
+
+
+def run_depth_edges(rm, name="depth_edges"):
+    """per view and select_grids = 0..4: the reference's ray_projection_depth rows (oracle == reference asserted before
+    anything is saved), the per-view row counts, and the scene aggregate of the reference's own
+    aggregate_2d_features_ray_marching (its call of ray_projection_depth given the fixture's step count: the loop itself
+    marches the default 300 steps)"""
+    sc = depth_edges_scene()
+    dims, vs, origin, stride, N = sc["dims"], sc["voxel_size"], sc["origin"], sc["stride"], sc["n_steps"]
+    feats, projs, tsdf = sc["features"], sc["projection"], sc["tsdf"]
+    V, C = feats.shape[0], feats.shape[2]
+    H, W = feats.shape[-2:]
+    pinv = [O.projection_inverse(O.scale_projection(projs[v, 0], stride)) for v in range(V)]
+    out = dict(features=feats[:, 0].numpy(), projection=projs[:, 0].numpy(), tsdf=tsdf[0, 0].numpy(),
+               dims=np.array(dims), voxel_size=np.float64(vs), origin=np.array(origin, dtype=np.float32),
+               stride=np.int64(stride), thr=np.float64(0.05), n_steps=np.int64(N), proj_inv=np.stack([p.numpy() for p in pinv]))
+    summary = {}
+    for k in range(5):
+        obj = R.make_raymarching(rm, dims, vs, origin, stride, rtype="depth", depth_points=k)
+        rows, counts = [], []
+        for v in range(V):
+            ps = O.scale_projection(projs[v], stride)
+            o_ref, d_ref = rm.get_ray_parameter(ps, feats[v])
+            o_or, d_or = O.ray_params(ps[0], H, W, pinv[v])
+            eq(o_or, o_ref[0, :, 0], f"o view {v}"); eq(d_or, d_ref[0], f"d view {v}")
+            ref, skip = ref_view_rows(obj.ray_projection_depth, ps, feats[v], tsdf, grids=N, select_grids=k)
+            orc = O.rma_depth_view(ps[0], feats[v, 0], tsdf[0, 0], dims, vs, origin, N, k, o_d=(o_or, d_or))
+            assert not skip, (k, v)                            # a one-row view is the quirk fixtures' case
+            if ref is None:
+                assert orc is None, (k, v)
+            else:
+                eq(orc, ref[0], f"depth rows k={k} view {v}")
+                rows.append(ref[0].numpy())
+            counts.append(0 if ref is None else ref[0].shape[0])
+        out[f"depth_k{k}_counts"] = np.array(counts, dtype=np.int64)
+        out[f"depth_k{k}_rows"] = np.concatenate(rows)
+        depth = obj.ray_projection_depth
+        obj.ray_projection_depth = lambda *a, _depth=depth, **kw: _depth(*a, grids=N, **kw)
+        obj.points_detection = []
+        obj.aggregate_2d_features_ray_marching(projs, feats, tsdf)
+        pts_ref = obj.points_detection[0]
+        pts_or = O.aggregate_rma(projs[:, 0], feats[:, 0], tsdf[0, 0], dims, vs, origin, stride, N, mode="depth", select_grids=k,
+                                 proj_inv=torch.stack(pinv))
+        eq(pts_or, pts_ref, f"depth aggregate k={k}")
+        out[f"depth_k{k}_points"] = pts_ref.numpy()
+        summary[k] = counts
+    # the last step inside the grid (helpers.depth_last_step_variant: its camera and TSDF are functions of the inputs above;
+    # the maps are those of view 0): the inverse and the reference's rows
+    from helpers import depth_edge_facts, depth_last_step_facts, depth_last_step_variant, load_golden
+    proj_l, tsdf_l = depth_last_step_variant(dict(dims=dims, voxel_size=vs, origin=origin, stride=stride, features=out["features"]))
+    ps = O.scale_projection(proj_l, stride)
+    pinv_l = O.projection_inverse(ps[0])
+    out["proj_inv_last_step"] = pinv_l.numpy()[None]
+    obj = R.make_raymarching(rm, dims, vs, origin, stride, rtype="depth")
+    for k in range(5):
+        ref, skip = ref_view_rows(obj.ray_projection_depth, ps, feats[0], tsdf_l.view(1, 1, *dims), grids=N, select_grids=k)
+        orc = O.rma_depth_view(ps[0], feats[0, 0], tsdf_l, dims, vs, origin, N, k, o_d=O.ray_params(ps[0], H, W, pinv_l))
+        assert not skip and ref is not None
+        eq(orc, ref[0], f"last-step rows k={k}")
+        out[f"last_step_k{k}_rows"] = ref[0].numpy()
+    path = os.path.join(HERE, f"rma_{name}.npz")
+    np.savez_compressed(path, **out)
+    g = load_golden(name)
+    facts, last = depth_edge_facts(g), depth_last_step_facts(g)
+    print(f"rma_{name}.npz: V={V} rows/view per k={summary} ({os.path.getsize(path)} bytes)\n  edges: {facts}\n"
+          f"  last step: {last[0]} rays inside for all {N} steps without a hit, {last[1]} rays hit")
+    assert facts["miss_hits"] == 0 and all(n > 0 for key, n in facts.items() if key != "miss_hits"), facts
+    assert min(last) > 0, last
+
+
 def run_decode(head_mod):
     """a12: _bbox_pred_to_bbox for the 6-DoF and the 8->7 'fcaf3d' yaw parametrisation + compute_centerness."""
     g = torch.Generator().manual_seed(3)
@@ -524,6 +638,7 @@ def main():
     run_quirk_scene(rm, "edge_single_sample_v1", quirk_neus_scene(1))
     run_quirk_scene(rm, "edge_single_sample_depth", quirk_depth_scene())
     run_quirk_single_view(rm, "edge_single_sample_only", quirk_neus_scene(0))
+    run_depth_edges(rm)
     run_decode(head)
     run_point_transforms(tr)
     run_atlas3d()
@@ -545,6 +660,10 @@ if __name__ == "__main__" and "--quirks" in sys.argv:
 if __name__ == "__main__" and "--edges" in sys.argv:
     _rm, _, _tr, _ = R.load_reference()
     run_edge_scenes(_rm, _tr)
+    sys.exit(0)
+
+if __name__ == "__main__" and "--depth-edges" in sys.argv:
+    run_depth_edges(R.load_reference()[0])
     sys.exit(0)
 
 if __name__ == "__main__" and "--atlas3d" in sys.argv:

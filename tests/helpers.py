@@ -214,3 +214,104 @@ def capacity_tensor(c, f, ts, device, cap=None, value=POISON, n_batch=None, comp
         F = poison_rows(f, cap, device, value)
     cs.compact = compact
     return S.SparseTensor(F, cs)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# depth-mode edge fixture (tests/golden/make_golden.py run_depth_edges; tests/test_rma_depth_edges_*.py)
+# ---------------------------------------------------------------------------------------------------------------------
+def look_at_projection(eye, target, f, cx, cy, up=(0.0, 0.0, 1.0)):
+    """[3,4] fp32 projection K @ [R | -R eye] in full-resolution pixels of a pinhole camera at `eye` looking at `target`
+    (camera rows right, down, forward; `up` must not be parallel to the viewing direction)"""
+    eye, target = np.asarray(eye, np.float64), np.asarray(target, np.float64)
+    fwd = (target - eye) / np.linalg.norm(target - eye)
+    right = np.cross(fwd, np.asarray(up, np.float64))
+    right /= np.linalg.norm(right)
+    R = np.stack([right, np.cross(fwd, right), fwd])
+    K = np.array([[f, 0, cx], [0, f, cy], [0, 0, 1.0]])
+    return torch.from_numpy((K @ np.concatenate([R, (-R @ eye)[:, None]], axis=1)).astype(np.float32))
+
+
+DEPTH_EDGES = "depth_edges"
+DEPTH_EDGE_VIEWS = dict(inside=0, far15=1, miss=2, far25=3, axis=4)        # view order of the fixture
+DEPTH_EDGE_KS = (0, 1, 2, 3, 4)
+
+
+def depth_oracle_views(g, feats, tsdf, k, n_steps=None, projection=None, proj_inv=None):
+    """the oracle's depth rows of every view of a depth_edges-like scene (ray parameters pinned through proj_inv; no one-row
+    quirk: what rma_view_rows returns): (rows [M, 4+C] numpy, per-view counts, per-view debug dicts)"""
+    from oracle import rma_oracle as O
+    H, W = feats.shape[-2:]
+    projection = t(g["projection"]) if projection is None else projection
+    proj_inv = t(g["proj_inv"]) if proj_inv is None else proj_inv
+    rows, counts, dbgs = [], [], []
+    for v in range(feats.shape[0]):
+        ps = O.scale_projection(projection[v], g["stride"])
+        r, dbg = O.rma_depth_view(ps, feats[v], tsdf, g["dims"], g["voxel_size"], g["origin"], g["n_steps"] if n_steps is None else n_steps,
+                                  k, o_d=O.ray_params(ps, H, W, proj_inv[v]), reference_quirks=False, return_debug=True)
+        counts.append(0 if r is None else r.shape[0])
+        dbgs.append(dbg)
+        if r is not None:
+            rows.append(r)
+    return (torch.cat(rows) if rows else torch.zeros(0, 4 + feats.shape[1])).numpy(), counts, dbgs
+
+
+def depth_last_step_variant(g):
+    """the one geometry in which a ray's LAST sample is still inside the grid (t_max is the grid's diagonal): a camera just
+    inside the outer corner of voxel (0,0,0) looking at the opposite corner, on a TSDF that is negative everywhere.  A ray that
+    stays inside for all N steps has no sign change -- the product appended at N-1 is 1 (:876-878), not tsdf * "outside" --
+    and gives no row; the rays beside it leave the grid early and hit there.  Returns (projection [1,3,4], tsdf [X,Y,Z])."""
+    dims, vs, org, s = g["dims"], g["voxel_size"], np.array(g["origin"], np.float64), g["stride"]
+    H, W = g["features"].shape[-2:]
+    corner = org - 0.5 * vs
+    proj = look_at_projection(corner + 0.05 * vs, corner + vs * np.array(dims, np.float64), s * 100.0, s * (W // 2), s * (H // 2))
+    return proj.view(1, 3, 4), torch.full(dims, -0.5)
+
+
+def depth_last_step_facts(g, k=4):
+    """(rays whose N samples are all inside the grid and that have no hit, rays that hit) of depth_last_step_variant"""
+    proj, tsdf = depth_last_step_variant(g)
+    pinv = t(g["proj_inv_last_step"])
+    _, _, dbg = depth_oracle_views(g, t(g["features"][:1]), tsdf, k, projection=proj, proj_inv=pinv)
+    inside = dbg[0]["valid"].all(dim=1)
+    return int((inside & ~dbg[0]["hit"]).sum()), int(dbg[0]["hit"].sum())
+
+
+def depth_edge_facts(g):
+    """what the depth_edges fixture is for, re-derived from its inputs with the oracle.  Every count but `miss_hits` must be
+    non-zero: rays of the inside view whose first sign change is at step 0, and their slots with sel < 0 at k = 4; hits of the
+    far views at N-2 and N-3, and their slots with sel >= N at k = 2; hit rays that enter the grid straight into a voxel with
+    tsdf <= 0 (the change sits at the step before entry); rays of the axis view with an exactly-zero direction component, and
+    its hits; rays that sample a NaN voxel, and hit rays with a NaN sample before their first change (a NaN product is no
+    change); first changes whose product is zero through a +0.0 and through a -0.0 voxel; rays that sample a voxel of
+    exactly 1.0 (the value that also stands for "outside")"""
+    N = g["n_steps"]
+    feats, tsdf = t(g["features"]), t(g["tsdf"])
+    vw = DEPTH_EDGE_VIEWS
+    _, _, d4 = depth_oracle_views(g, feats, tsdf, 4)
+    _, _, d2 = depth_oracle_views(g, feats, tsdf, 2)
+    f = dict(enter_nonpositive=0, nan_rays=0, nan_before_change=0, change_on_pos_zero=0, change_on_neg_zero=0, one_sampled=0)
+    steps = torch.arange(N).view(1, -1)
+    for dbg in d4:
+        hit, best, sdf, valid = dbg["hit"], dbg["best"], dbg["sdf"], dbg["valid"]
+        r = torch.nonzero(hit)[:, 0]
+        b = best[r]
+        f["enter_nonpositive"] += int((~valid[r, b] & valid[r, b + 1] & (sdf[r, b + 1] <= 0)).sum())
+        nan = valid & torch.isnan(sdf)
+        f["nan_rays"] += int(nan.any(dim=1).sum())
+        f["nan_before_change"] += int((hit & (nan & (steps <= best.view(-1, 1))).any(dim=1)).sum())
+        pair = torch.stack((sdf[r, b], sdf[r, b + 1]), dim=1)
+        zero, neg = pair == 0, torch.signbit(pair)
+        f["change_on_pos_zero"] += int((zero & ~neg).any(dim=1).sum())
+        f["change_on_neg_zero"] += int((zero & neg).any(dim=1).sum())
+        f["one_sampled"] += int((valid & (sdf == 1.0)).any(dim=1).sum())
+    i, a = d4[vw["inside"]], d4[vw["axis"]]
+    f["inside_best0"] = int((i["hit"] & (i["best"] == 0)).sum())
+    f["inside_sel_below0"] = int((i["hit"].view(-1, 1) & (i["sel"] < 0)).sum())
+    f["far15_at_Nm2"] = int((d4[vw["far15"]]["hit"] & (d4[vw["far15"]]["best"] == N - 2)).sum())
+    f["far25_at_Nm3"] = int((d4[vw["far25"]]["hit"] & (d4[vw["far25"]]["best"] == N - 3)).sum())
+    f["far25_at_Nm2"] = int((d4[vw["far25"]]["hit"] & (d4[vw["far25"]]["best"] == N - 2)).sum())
+    f["far_sel_from_N"] = sum(int((d2[vw[n]]["hit"].view(-1, 1) & (d2[vw[n]]["sel"] >= N)).sum()) for n in ("far15", "far25"))
+    f["axis_zero_dir"] = int((a["d"] == 0).any(dim=0).sum())
+    f["axis_hits"] = int(a["hit"].sum())
+    f["miss_hits"] = int(d4[vw["miss"]]["hit"].sum())
+    return f
