@@ -70,7 +70,10 @@ class _SigmoidBCELoss(nn.Module):
         self.loss_weight = loss_weight
 
     def forward(self, pred, target, avg_factor=None):
-        loss = nn.functional.binary_cross_entropy_with_logits(pred, target.float(), reduction="none")
+        # at least float32, and float64 under float64 logits: torch evaluates (1 - target) * pred in place in the target's type, so
+        # a float32 target would round a float64 evaluation of this loss to float32
+        target = target.to(torch.promote_types(pred.dtype, torch.float32))
+        loss = nn.functional.binary_cross_entropy_with_logits(pred, target, reduction="none")
         return self.loss_weight * loss.sum() / (avg_factor if avg_factor is not None else max(loss.numel(), 1))
 
 
@@ -87,6 +90,7 @@ class _IoU3DLoss(nn.Module):
             from ..core.rotated_iou import rotated_iou_3d
             iou = rotated_iou_3d(pred[:, :7], target[:, :7].to(pred.dtype))
         else:
+            target = target.to(pred.dtype)                      # like the rotated branch: a float64 evaluation upcasts the targets first
             p_lo, p_hi = pred[:, :3] - pred[:, 3:6] / 2, pred[:, :3] + pred[:, 3:6] / 2
             t_lo, t_hi = target[:, :3] - target[:, 3:6] / 2, target[:, :3] + target[:, 3:6] / 2
             # products written out: prod()'s backward reads a scalar back (a host synchronisation inside loss.backward())

@@ -544,6 +544,235 @@ def run_decode(head_mod):
     print("decode.npz written")
 
 
+# --------------------------------------------------------------------------------------------------------------------
+# FCAF3D training targets and the composition of the three losses (fcaf3d_head.py:405-484, :142-214), boxes with yaw 0
+# --------------------------------------------------------------------------------------------------------------------
+ASSIGN_LIMIT, ASSIGN_TOPK = 27, 18
+
+
+def save_stable(path, arrays):
+    """np.savez_compressed with fixed member dates: numpy stamps every member with the wall clock, so its files differ from
+    run to run; this one is the same bytes for the same arrays"""
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED) as z:
+        for key, value in arrays.items():
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            with z.open(info, "w") as f:
+                np.lib.format.write_array(f, np.asarray(value), allow_pickle=False)
+
+
+def cells(n, step):
+    g = (torch.arange(n, dtype=torch.float32) + 0.5) * step
+    return torch.stack(torch.meshgrid(g, g, g, indexing="ij"), -1).reshape(-1, 3).contiguous()
+
+
+def gt_row(cx, cy, cz, dx, dy, dz):
+    """(x, y, z_bottom, dx, dy, dz, yaw = 0) of the box with gravity centre (cx, cy, cz)"""
+    return [cx, cy, cz - dz / 2, dx, dy, dz, 0.0]
+
+
+class GTStandIn:
+    """the three attributes of DepthInstance3DBoxes the reference's assigner reads (mmdet3d is absent): tensor [m, 7] =
+    (x, y, z_bottom, dx, dy, dz, yaw), volume = dx dy dz, gravity_center = the bottom centre lifted by dz / 2"""
+
+    def __init__(self, rows):
+        self.tensor = torch.tensor(rows, dtype=torch.float32).view(-1, 7)
+        self.volume = self.tensor[:, 3] * self.tensor[:, 4] * self.tensor[:, 5]
+        self.gravity_center = self.tensor[:, :3].clone()
+        self.gravity_center[:, 2] += self.tensor[:, 5] / 2
+
+    def __len__(self):
+        return len(self.tensor)
+
+
+def rotation_stand_in(points, angles, axis=0):
+    """rotation_3d_in_axis for boxes without yaw: the identity, whatever convention the third-party function follows"""
+    assert (angles == 0).all(), "the assignment fixture holds boxes with yaw 0 only"
+    return points
+
+
+def ieee_sqrt(x):
+    return torch.from_numpy(np.sqrt(x.detach().numpy()))
+
+
+def assign_scenes():
+    """name -> (levels, box rows, labels, limit, topk); every box has yaw 0 and a label of its own"""
+    lattice = [cells(n, s) for n, s in ((12, .08), (6, .16), (3, .32), (2, .64))]
+    rng = np.random.RandomState(11)
+    random_levels = [torch.from_numpy(rng.uniform(0, 2, (n, 3)).astype(np.float32)) for n in (3001, 777, 130, 65)]
+    random_rows = [gt_row(*rng.uniform(.3, 1.7, 3), *rng.uniform(.25, 1.4, 3)) for _ in range(5)]
+    rng = np.random.RandomState(12)
+    gap_levels = [torch.from_numpy(rng.uniform(0, 2, (n, 3)).astype(np.float32)) for n in (900, 0, 70, 9)]
+    gap_rows = [gt_row(*rng.uniform(.5, 1.5, 3), *rng.uniform(.3, 1.6, 3)) for _ in range(4)]
+    # the unit box around (1, 1, 1): three points on a face, one on a corner (a face distance of exactly 0: not inside), one
+    # a single ulp inside.  Fewer than topk + 1 candidates, so every inside point of level 0 passes the k-th value of -1 -- a
+    # face point taken for an inside point would become a positive row
+    on_face = torch.tensor([[1.5, 1.0, 1.0], [0.5, 1.0, 1.25], [1.0, 1.0, 1.5], [1.5, 1.5, 1.5],
+                            [float(np.nextafter(np.float32(1.5), np.float32(0))), 1.0, 1.0]])
+    pts7 = cells(2, .3)[:7]
+    return {
+        # k-th-value ties (a box centred on a lattice plane), a box nested in it, a far box, the equal-volume duplicate
+        "lattice": (lattice, [gt_row(.48, .48, .48, .64, .64, .64), gt_row(.40, .44, .45, .30, .30, .30),
+                              gt_row(5.0, 5.0, 5.0, .50, .50, .50), gt_row(.48, .48, .48, .64, .64, .64)], [3, 7, 2, 5],
+                    ASSIGN_LIMIT, ASSIGN_TOPK),
+        # >= limit on every level (-> the last), < limit on level 0 (-> -1, clamped to 0), >= limit on levels 0 and 1 only (-> 1)
+        "best_level": (lattice[:3], [gt_row(.48, .48, .48, 2.0, 2.0, 2.0), gt_row(.30, .30, .30, .17, .17, .17),
+                                     gt_row(.60, .60, .60, .60, .60, .60)], [1, 2, 3], ASSIGN_LIMIT, ASSIGN_TOPK),
+        # n = 7 < topk + 1, on three levels and on one
+        "few_points": ([pts7[:4].clone(), pts7[4:6].clone(), pts7[6:].clone()], [gt_row(.3, .3, .3, 1.0, 1.0, 1.0)], [4],
+                       ASSIGN_LIMIT, ASSIGN_TOPK),
+        "few_points_one_level": ([pts7.clone()], [gt_row(.31, .27, .34, 1.0, 1.0, 1.0)], [4], ASSIGN_LIMIT, ASSIGN_TOPK),
+        "random": (random_levels, random_rows, [6, 0, 17, 9, 12], ASSIGN_LIMIT, ASSIGN_TOPK),
+        "random_top1_limit1": (random_levels, random_rows, [6, 0, 17, 9, 12], 1, 1),
+        "empty_middle_level": (gap_levels, gap_rows, [8, 1, 15, 4], ASSIGN_LIMIT, ASSIGN_TOPK),
+        "point_on_face": ([torch.cat((cells(4, .5), on_face)), cells(2, 1.0)], [gt_row(1.0, 1.0, 1.0, 1.0, 1.0, 1.0)], [13],
+                          ASSIGN_LIMIT, ASSIGN_TOPK),
+    }
+
+
+def run_assign(head_mod):
+    """the reference's FCAF3DAssigner.assign on scenes of yaw-0 boxes.  Per scene: the level point arrays, the box rows, their
+    labels, (limit, topk), the labels of all rows (int16) and, for the rows with label >= 0 in ascending order, the box target
+    [P, 7] and the centerness target [P]; the box of a row is told by its label.
+    Two things stand in for what is absent.  rotation_3d_in_axis (mmdet3d) is the identity, asserted to be called with zero
+    angles only: exact for any convention of that function, so the convention stays UNPINNED by this fixture.  torch.sqrt is
+    numpy's correctly rounded one during the run (a torch primitive, not reference code): the CPU's vector library is within
+    one ulp but which values it misses depends on the processor."""
+    from unittest import mock
+    head_mod.rotation_3d_in_axis = rotation_stand_in
+    out, names = {}, []
+    for name, (levels, rows, labels, limit, topk) in assign_scenes().items():
+        assert len(set(labels)) == len(labels) and all(r[6] == 0.0 for r in rows)
+        gt = GTStandIn(rows)
+        with mock.patch.object(torch, "sqrt", ieee_sqrt):
+            ctr, box_t, lab = head_mod.FCAF3DAssigner(limit, topk, len(levels)).assign(levels, gt, torch.tensor(labels))
+        pos = torch.nonzero(lab >= 0).view(-1)
+        assert ctr.dtype == box_t.dtype == torch.float32 and len(lab) == sum(len(p) for p in levels)
+        for i, p in enumerate(levels):
+            out[f"assign.{name}.level{i}"] = p.numpy()
+        out[f"assign.{name}.boxes"] = gt.tensor.numpy()
+        out[f"assign.{name}.gt_labels"] = np.array(labels, dtype=np.int16)
+        out[f"assign.{name}.limit_topk"] = np.array([limit, topk], dtype=np.int32)
+        out[f"assign.{name}.labels"] = lab.numpy().astype(np.int16)
+        out[f"assign.{name}.pos_box_target"] = box_t[pos].numpy()
+        out[f"assign.{name}.pos_centerness"] = ctr[pos].numpy()
+        names.append(name)
+        print(f"  assign {name}: levels {[len(p) for p in levels]}, {len(rows)} boxes, limit {limit}, topk {topk}: "
+              f"{len(pos)} positive rows, labels {sorted(set(lab[pos].tolist()))}")
+    out["assign.names"] = np.array(names)
+    # the premises the scenes are for, on the reference's own output
+    count = lambda name, label: int((out[f"assign.{name}.labels"] == label).sum())
+    assert 0 < count("lattice", 3) and 0 < count("lattice", 7) and count("lattice", 2) == 0 and count("lattice", 5) == 0
+    lattice = assign_scenes()["lattice"]                     # ties at the k-th value: alone, box 0 keeps fewer than topk rows
+    with mock.patch.object(torch, "sqrt", ieee_sqrt):
+        alone = head_mod.FCAF3DAssigner(ASSIGN_LIMIT, ASSIGN_TOPK, 4).assign(lattice[0], GTStandIn(lattice[1][:1]), torch.tensor([3]))[2]
+    assert 0 < int((alone >= 0).sum()) < ASSIGN_TOPK
+    assert all(count("best_level", label) > 0 for label in (1, 2, 3))
+    assert count("few_points", 4) == 4 and count("few_points_one_level", 4) == 6
+    assert count("point_on_face", 13) == 9 and (out["assign.point_on_face.labels"][64:68] == -1).all()
+    assert 0 < (out["assign.random_top1_limit1.labels"] >= 0).sum() <= 5 < (out["assign.random.labels"] >= 0).sum()
+    assert (out["assign.empty_middle_level.labels"] >= 0).any()
+    return out
+
+
+def loss_stand_ins(record):
+    """the three mmdet losses the shipped configuration names, written out in float64 numpy (mmdet is absent): sigmoid focal
+    loss (gamma 2, alpha 0.25), sigmoid cross entropy, axis-aligned IoU3D loss -- each sum / avg_factor.  Every call's
+    arguments go to `record`.  The formulas are NOT what this fixture pins; which rows, targets, weights and normalisers the
+    reference hands them is."""
+    as64 = lambda t: t.detach().double().numpy()
+    softplus_neg_abs = lambda x: np.log1p(np.exp(-np.abs(x)))
+
+    def focal(pred, labels, avg_factor=None):
+        x, lab = as64(pred), labels.numpy()
+        t = np.zeros_like(x)
+        hit = (lab >= 0) & (lab < x.shape[1])
+        t[np.nonzero(hit)[0], lab[hit]] = 1.0
+        p = 1.0 / (1.0 + np.exp(-x))
+        pt = (1 - p) * t + p * (1 - t)
+        loss = (np.maximum(x, 0) - x * t + softplus_neg_abs(x)) * (0.25 * t + 0.75 * (1 - t)) * pt ** 2.0
+        record.append(dict(cls_labels=lab.astype(np.int16), cls_avg_factor=np.float64(avg_factor)))
+        return torch.tensor(loss.sum() / float(avg_factor), dtype=torch.float64)
+
+    def bce(pred, target, avg_factor=None):
+        x, t = as64(pred), as64(target)
+        assert x.shape == t.shape
+        record[-1].update(ctr_logit=x[:, 0], ctr_target=target.numpy()[:, 0], ctr_avg_factor=np.float64(avg_factor))
+        return torch.tensor((np.maximum(x, 0) - x * t + softplus_neg_abs(x)).sum() / float(avg_factor), dtype=torch.float64)
+
+    def iou3d(pred, target, weight=None, avg_factor=None):
+        a, b, w = as64(pred), as64(target), as64(weight)
+        ov = np.clip(np.minimum(a[:, :3] + a[:, 3:6] / 2, b[:, :3] + b[:, 3:6] / 2)
+                     - np.maximum(a[:, :3] - a[:, 3:6] / 2, b[:, :3] - b[:, 3:6] / 2), 0, None).prod(1)
+        iou = ov / np.clip(a[:, 3:6].prod(1) + b[:, 3:6].prod(1) - ov, 1e-8, None)
+        record[-1].update(box_pred=a, box_target=target.numpy(), box_weight=weight.numpy(), box_avg_factor=np.float64(avg_factor))
+        return torch.tensor(((1 - iou) * w).sum() / float(avg_factor), dtype=torch.float64)
+
+    return focal, bce, iou3d
+
+
+def loss_scenes():
+    """two scenes of four levels (6^3 / 4^3 / 2^3 / 1 cell centres) for one call of loss(): per scene the head outputs of every
+    level (float64 values on a 1/16 grid, 6 regression outputs), the points, the box rows and labels.  The second scene's only
+    box lies far from every point: no positive row"""
+    rng = np.random.RandomState(21)
+    pts = [cells(n, s) for n, s in ((6, .16), (4, .24), (2, .48), (1, .96))]
+    grid = lambda a: torch.from_numpy(np.round(a * 16) / 16)
+    scenes = []
+    for rows, labels in (([gt_row(.45, .50, .42, .70, .62, .66), gt_row(.30, .62, .55, .28, .30, .26), gt_row(.66, .30, .30, .40, .34, .44)],
+                          [5, 16, 0]), ([gt_row(4.0, 4.0, 4.0, .5, .5, .5)], [9])):
+        scenes.append(dict(centerness=[grid(rng.randn(len(p), 1)) for p in pts],
+                           bbox_pred=[grid(rng.uniform(.05, .45, (len(p), 6))) for p in pts],
+                           cls_score=[grid(rng.randn(len(p), 18) * 2 - 3) for p in pts], points=pts, rows=rows, labels=labels))
+    return scenes
+
+
+def run_head_loss(head_mod):
+    """the reference's own FCAF3DHead.loss (:142-214) on loss_scenes(): the head is built by __new__ with the reference's
+    assigner and loss_stand_ins().  Stored: the inputs, the three losses (float64) and what the reference handed each stand-in
+    per scene -- the labels of all rows, the positive rows' logits, targets, decoded boxes and weights, and the avg_factors.
+    The head outputs are float64 (values exact in float32), the points float32: the assignment runs in float32 like run_assign
+    (same two stand-ins), everything after it in float64."""
+    from unittest import mock
+    head_mod.rotation_3d_in_axis = rotation_stand_in
+    scenes, record, out = loss_scenes(), [], {}
+    h = head_mod.FCAF3DHead.__new__(head_mod.FCAF3DHead)
+    h.yaw_parametrization = "fcaf3d"
+    h.assigner = head_mod.FCAF3DAssigner(ASSIGN_LIMIT, ASSIGN_TOPK, 4)
+    h.loss_cls, h.loss_centerness, h.loss_bbox = loss_stand_ins(record)
+    per_level = lambda key: [[sc[key][l] for sc in scenes] for l in range(4)]
+    with mock.patch.object(torch, "sqrt", ieee_sqrt):
+        loss = h.loss(per_level("centerness"), per_level("bbox_pred"), per_level("cls_score"), per_level("points"),
+                      [GTStandIn(sc["rows"]) for sc in scenes], [torch.tensor(sc["labels"]) for sc in scenes])
+    assert len(record) == 2 and "box_pred" in record[0] and "box_pred" not in record[1]      # scene 1 took the else branch
+    assert (record[1]["cls_labels"] == -1).all() and record[1]["cls_avg_factor"] == 1.0
+    for k in ("loss_centerness", "loss_bbox", "loss_cls"):
+        assert loss[k].dtype == torch.float64
+        out[f"loss.{k}"] = np.float64(loss[k])
+    for s, (sc, rec) in enumerate(zip(scenes, record)):
+        for l in range(4):
+            out[f"loss.scene{s}.points{l}"] = sc["points"][l].numpy()
+            for key in ("centerness", "bbox_pred", "cls_score"):
+                out[f"loss.scene{s}.{key}{l}"] = sc[key][l].numpy().astype(np.float32)
+                assert (out[f"loss.scene{s}.{key}{l}"] == sc[key][l].numpy()).all()
+        out[f"loss.scene{s}.boxes"] = np.array(sc["rows"], dtype=np.float32)
+        out[f"loss.scene{s}.gt_labels"] = np.array(sc["labels"], dtype=np.int16)
+        for key, value in rec.items():
+            out[f"loss.scene{s}.handed.{key}"] = value
+    print(f"  loss: {({k: float(v) for k, v in loss.items()})}; positive rows per scene "
+          f"{[int((r['cls_labels'] >= 0).sum()) for r in record]}, avg_factors "
+          f"{[(float(r['cls_avg_factor']), float(r.get('box_avg_factor', 'nan'))) for r in record]}")
+    return out
+
+
+def run_targets(head_mod):
+    out = dict(run_assign(head_mod), **run_head_loss(head_mod))
+    path = os.path.join(HERE, "fcaf3d_assign.npz")
+    save_stable(path, out)
+    print(f"fcaf3d_assign.npz written ({os.path.getsize(path)} bytes)")
+
+
 def run_point_transforms(tr):
     """a8 train path: the point helpers of fcaf3d_transforms.py:152-200 on seeded points"""
     g = torch.Generator().manual_seed(9)
@@ -640,6 +869,7 @@ def main():
     run_quirk_single_view(rm, "edge_single_sample_only", quirk_neus_scene(0))
     run_depth_edges(rm)
     run_decode(head)
+    run_targets(head)
     run_point_transforms(tr)
     run_atlas3d()
     run_backbone2d()
@@ -664,6 +894,10 @@ if __name__ == "__main__" and "--edges" in sys.argv:
 
 if __name__ == "__main__" and "--depth-edges" in sys.argv:
     run_depth_edges(R.load_reference()[0])
+    sys.exit(0)
+
+if __name__ == "__main__" and "--targets" in sys.argv:
+    run_targets(R.load_reference()[1])
     sys.exit(0)
 
 if __name__ == "__main__" and "--atlas3d" in sys.argv:
