@@ -20,6 +20,9 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma.h")
 # the data-preparation surface: a library and a header of their own (include/cnrma_prep.h), bound the same way
 PREP_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_prep_hip.so")
 PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_prep.h")
+# the evaluation surface (indoor mAP of the detections): include/cnrma_eval.h and its own library, bound the same way
+EVAL_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_eval_hip.so")
+EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_eval.h")
 # the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
 _CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
@@ -75,6 +78,14 @@ except OSError as e:
 if _prep_exp:
     raise CnrmaError(f"cnrma_prep.h declares experiment entry points ({sorted(_prep_exp)}): the preparation library has none")
 PREP_ABI_VERSION = PREP_CONSTANTS["CNRMA_PREP_ABI_VERSION"]
+try:
+    with open(EVAL_HEADER_PATH) as _f:
+        EVAL_SIGNATURES, _eval_exp, EVAL_CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {EVAL_HEADER_PATH}: {e}") from e
+if _eval_exp:
+    raise CnrmaError(f"cnrma_eval.h declares experiment entry points ({sorted(_eval_exp)}): the evaluation library has none")
+EVAL_ABI_VERSION = EVAL_CONSTANTS["CNRMA_EVAL_ABI_VERSION"]
 
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
@@ -130,6 +141,36 @@ def call_prep(name, *args):
     rc = getattr(load_prep(), name)(*args)
     if rc != 0:
         raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == PREP_CONSTANTS["CNRMA_PREP_EINVAL"]
+                                                          else " (-hipError_t)"))
+    return rc
+
+
+_eval_lib = None
+
+
+def load_eval():
+    """libcnrma_eval_hip.so (include/cnrma_eval.h), loaded once; raises loudly when it is not built"""
+    global _eval_lib
+    if _eval_lib is not None:
+        return _eval_lib
+    if not os.path.exists(EVAL_LIB_PATH):
+        raise CnrmaError(f"{EVAL_LIB_PATH} not found: build it with `python __graft_entry__.py build` "
+                         f"(or `make -C cn-rma_amd/csrc`). There is no CPU fallback for the product path.")
+    lib = ctypes.CDLL(EVAL_LIB_PATH)
+    for name, (res, args) in EVAL_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    if lib.cnrma_eval_abi_version() != EVAL_ABI_VERSION:
+        raise CnrmaError("ABI version mismatch (libcnrma_eval_hip.so)")
+    _eval_lib = lib
+    return lib
+
+
+def call_eval(name, *args):
+    rc = getattr(load_eval(), name)(*args)
+    if rc != 0:
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == EVAL_CONSTANTS["CNRMA_EVAL_EINVAL"]
                                                           else " (-hipError_t)"))
     return rc
 

@@ -9,6 +9,7 @@ import torch
 
 from . import _lib
 from ._lib import call, ptr, stream
+from .evaluate import DetectionEvaluator, indoor_eval_device  # noqa: F401  (the device evaluator: include/cnrma_eval.h)
 
 
 def box_iou(a, b, rotated=True, mode3d=True):
