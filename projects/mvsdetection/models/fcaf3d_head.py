@@ -192,7 +192,13 @@ class FCAF3DHead(nn.Module):
         return zip(*outs[::-1])
 
     def _prune(self, x, scores):
-        """keep the top `pts_threshold` rows per scene by the interpolated max-class score of the coarser level"""
+        """keep the top `pts_threshold` rows per scene by the interpolated max-class score of the coarser level (reference
+        :123-139).  A scene with no more rows than that keeps them all; of rows with equal scores those with the smaller row
+        index stay (the reference's topk(sorted=False) leaves the choice open); the kept rows stay in row order.
+        pts_threshold < 0 switches the step off.  All four forms below -- eager with one scene / with several, static trace with
+        one scene / with several -- keep the same rows: tests/test_head_select_gpu.py pins them row for row.
+        Static trace: the plan flag True (no calibration scene was pruned) returns x itself and registers `rows per scene <=
+        pts_threshold`; False and None prune under the live-count word, into a capacity of min(B * pts_threshold, capacity of x)."""
         if self.pts_threshold < 0:
             return x
         plan = P.current()
@@ -342,7 +348,12 @@ class FCAF3DHead(nn.Module):
         count is read back.  Per level the branch of the calibration run is replayed -- more rows than nms_pre: the
         nms_pre best by max class score x centerness (dead rows ranked -inf), else all rows -- and its premise registered.
         Returns (bboxes [K,6|7], scores [K,n_cls], valid int32 [L], sizes): level l owns rows [sum(sizes[:l]), +sizes[l]) of
-        which the first valid[l] are detections (the reference's row order within the level)."""
+        which the first valid[l] are detections.  Order within a level, as in the reference: a level that is cut gives its
+        nms_pre best rows, best first, equal scores by ascending row index (torch.topk leaves ties open); a level that is not
+        gives its live rows in row order.  Flag True: sizes[l] = nms_pre, valid[l] = min(n, nms_pre), premise n > nms_pre.  Flag
+        False (and nms_pre <= 0): sizes[l] = the capacity, valid[l] = n, premise n <= nms_pre.  Flag None on a capacity above
+        nms_pre: the cut form whatever n is -- the one deviation from the reference's order: n <= nms_pre live rows come best
+        first instead of in row order (the same row set, valid[l] = n).  tests/test_head_select_gpu.py pins all of this."""
         plan = P.current()
         nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
         boxes, scores, valid, sizes = [], [], [], []
@@ -410,7 +421,11 @@ class FCAF3DHead(nn.Module):
     def get_bboxes_fused(self, centernesses, bbox_preds, cls_scores, points, scenes, n_scenes):
         """decode of forward(..., fused=True): per level ONE row set for all scenes + the rows' scene ids.  Per scene the
         nms_pre best rows by max class score x centerness are picked with the other scenes masked out (reference
-        _get_bboxes_single :247-256 per scene).  Returns [(bboxes, scores)] per scene."""
+        _get_bboxes_single :247-256 per scene).  Returns [(bboxes, scores)] per scene, the levels concatenated, within a level
+        in the reference's order: a scene with more than nms_pre > 0 rows on the level gives its nms_pre best, best first, equal
+        scores by ascending row index; any other scene gives all its rows in row order (the reference only cuts, and so only
+        reorders, when there are more).  Row for row what _get_bboxes_single gives for that scene alone
+        (tests/test_head_select_gpu.py)."""
         nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
         per_scene = [([], []) for _ in range(n_scenes)]
         for cen, box, cls, pts, cs in zip(centernesses, bbox_preds, cls_scores, points, scenes):
@@ -423,13 +438,14 @@ class FCAF3DHead(nn.Module):
                 groups = [ids]
             else:
                 # ONE stable sort per level on the key (scene, descending score): every scene's rows become a contiguous
-                # run in rank order, of which the first nms_pre are taken (scores are >= 0: their bit patterns order them)
+                # run in rank order, of which the first nms_pre are taken (scores are >= 0: their bit patterns order them);
+                # a scene that is not cut gives its whole run, put back into row order
                 counts = cs.batch_counts()                  # usually cached by the pruning step of the same level
                 bits = S.max_scores(cls, cen).view(torch.int32).long()
                 order = torch.sort((sc.long() << 32) | (0xFFFFFFFF - bits), stable=True)[1]
                 groups, r0 = [], 0
                 for nb in counts:
-                    groups.append(order[r0:r0 + (min(nb, nms_pre) if nms_pre > 0 else nb)])
+                    groups.append(order[r0:r0 + nms_pre] if nb > nms_pre > 0 else torch.sort(order[r0:r0 + nb])[0])
                     r0 += nb
             for b, ids in enumerate(groups):
                 bx, scr = S.select_decode(ids, cls, cen, box, pts, self.yaw_parametrization)
