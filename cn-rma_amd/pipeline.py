@@ -168,8 +168,7 @@ def forward_scene(cfg, backbone, head, features_nchw, projections, tsdf, offset=
     tm.mark("backbone")
     cen, box, cls, pts = map(list, head(levels))
     tm.mark("head")
-    bboxes, scores = head._get_bboxes_single([c[0] for c in cen], [b[0] for b in box], [c[0] for c in cls],
-                                             [p[0] for p in pts])
+    bboxes, scores = head.get_bboxes_scene(cen, box, cls, pts)
     tm.mark("decode")
     out.update(bboxes=bboxes, scores=scores, M=info["M"], M_selected=info["M_selected"], M_unique=len(x),
                level_rows=[len(l) for l in levels], head_rows=[len(c[0]) for c in cen], stage_ms=tm.result())
@@ -269,7 +268,7 @@ def trace_net(plan, backbone, head, coords, feats, n_dev, voxel_size, device, ex
                head=dict(centerness=[c[0] for c in cen], bbox_pred=[b[0] for b in box], cls_score=[c[0] for c in cls],
                          points=[p[0] for p in pts], n_dev=[c[0].n_dev for c in css]))
     if nms is not None:
-        trace_nms(plan, out, nms, nms_state, (head.test_cfg.nms_pre or 0) if head.test_cfg is not None else 0)
+        trace_nms(plan, out, nms, nms_state, head.nms_pre)
     return out
 
 
@@ -344,8 +343,7 @@ class StaticNet(_StaticGraph):
                 x, _ = S.voxelize(coords, feats, self.voxel_size)
                 levels = self.backbone(x)
                 cen, box, cls, pts = map(list, self.head(levels))
-                bboxes, scores = self.head._get_bboxes_single([c[0] for c in cen], [b[0] for b in box], [c[0] for c in cls],
-                                                              [p[0] for p in pts])
+                bboxes, scores = self.head.get_bboxes_scene(cen, box, cls, pts)
             self.plan = plan
             M, C = feats.shape
             self.cap = int(cap or M)

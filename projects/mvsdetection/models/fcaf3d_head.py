@@ -107,6 +107,24 @@ class _IoU3DLoss(nn.Module):
 from ..core.boxes import GTBoxes  # noqa: E402,F401  (kept importable from here: tests and the detector use it)
 
 
+def _cut_ids(cls, cen, nms_pre, n_dev=None):
+    """the pre-NMS cut of one scene's rows on one level (reference :247-256): more than nms_pre > 0 rows give the ids of the
+    nms_pre best by max class score x centerness (the ranking key only), best first, equal scores by ascending row index
+    (torch.topk leaves ties open); anything else gives None: every row, in row order.  n_dev (static trace): len(cls) is a
+    capacity and the rows behind the live count rank -inf; fewer than nms_pre live rows all come, best first, in front of
+    slots that repeat row 0."""
+    return S.topk_indices(S.max_scores(cls, cen), nms_pre, n_dev) if len(cls) > nms_pre > 0 else None
+
+
+def _rank_by_scene(scene, max_scores):
+    """the cut for several scenes in one row set: the rows by ONE stable sort on the key (scene, descending score).  The scores
+    are >= 0, so their bit patterns order them; equal scores stay in row order.  Every scene's rows become one contiguous run,
+    best first; rows given the scene id n_scenes (the dead rows of a static trace) sort behind every scene.  The first nms_pre
+    rows of a run are what _cut_ids gives for that scene alone; the run of a scene that is not cut goes back into row order (a
+    sort of its ids).  That is the caller's part: it finds the runs with host counts or through device-side offsets."""
+    return torch.sort((scene.long() << 32) | (0xFFFFFFFF - max_scores.view(torch.int32).long()), stable=True)[1]
+
+
 @HEADS.register_module()
 class FCAF3DHead(nn.Module):
     def __init__(self, n_classes, in_channels, out_channels, n_reg_outs, voxel_size, pts_threshold, assigner,
@@ -193,61 +211,59 @@ class FCAF3DHead(nn.Module):
 
     def _prune(self, x, scores):
         """keep the top `pts_threshold` rows per scene by the interpolated max-class score of the coarser level (reference
-        :123-139).  A scene with no more rows than that keeps them all; of rows with equal scores those with the smaller row
-        index stay (the reference's topk(sorted=False) leaves the choice open); the kept rows stay in row order.
-        pts_threshold < 0 switches the step off.  All four forms below -- eager with one scene / with several, static trace with
-        one scene / with several -- keep the same rows: tests/test_head_select_gpu.py pins them row for row.
-        Static trace: the plan flag True (no calibration scene was pruned) returns x itself and registers `rows per scene <=
-        pts_threshold`; False and None prune under the live-count word, into a capacity of min(B * pts_threshold, capacity of x)."""
-        if self.pts_threshold < 0:
+        :123-139; the rule and its one body: _keep_mask).  pts_threshold < 0 switches the step off; a step that keeps every row
+        returns x itself.  Eagerly the host counts decide that, and the decision is recorded in the plan.  Static trace: the plan
+        flag True (no calibration scene was pruned) skips and registers `rows per scene <= pts_threshold`; False and None prune
+        under the live-count word, into a capacity of min(B * pts_threshold, capacity of x).  tests/test_head_select_gpu.py."""
+        T, B, plan = self.pts_threshold, x.cs.n_batch, P.current()
+        if T < 0:
             return x
-        plan = P.current()
-        if plan is not None and plan.static:
-            # static trace (one scene): the branch of the calibration run, its premise registered as an assumption
-            B = x.cs.n_batch
-            if plan.next_flag():                     # True: no calibration scene needed pruning; None (scenes differ) -> prune
-                if B <= 1:
-                    plan.watch(x.cs.n_dev, 0, self.pts_threshold)
-                else:                                # several scenes per pass: the premise holds per scene
-                    cnt, _ = x.cs.counts_dev()
-                    for b in range(B):
-                        plan.watch(cnt[b:b + 1], 0, self.pts_threshold)
-                return x
-            with torch.no_grad():
-                interpolated = S.interpolate(scores, x.C, x.cs.n_dev)
-                if B <= 1:
-                    mask = S.topk_mask(interpolated, self.pts_threshold, n_dev=x.cs.n_dev)   # keeps every row when n <= threshold
-                else:                                # per scene: the other scenes' rows ranked -inf and never kept
-                    flat, scene = interpolated.view(-1), x.C[:, 0]
-                    low = torch.full_like(flat, float("-inf"))
-                    mask = None
-                    for b in range(B):
-                        mine = scene == b
-                        m = S.topk_mask(torch.where(mine, flat, low), self.pts_threshold, n_dev=x.cs.n_dev) & mine.to(torch.uint8)
-                        mask = m if mask is None else mask | m
-            return S.prune(x, mask, n_keep=min(B * self.pts_threshold, x.cs.n))
-        with torch.no_grad():
-            counts = x.cs.batch_counts()
-            skip = all(c <= self.pts_threshold for c in counts)
+        static = plan is not None and plan.static
+        counts = None if static else x.cs.batch_counts()
+        if static:                                   # the branch of the calibration run, its premise registered as an assumption
+            skip = plan.next_flag()                  # True: no calibration scene needed pruning; None (scenes differ) -> prune
+            if skip and B <= 1:
+                plan.watch(x.cs.n_dev, 0, T)
+            elif skip:                               # several scenes per pass: the premise holds per scene
+                cnt, _ = x.cs.counts_dev()
+                for b in range(B):
+                    plan.watch(cnt[b:b + 1], 0, T)
+        else:
+            skip = all(c <= T for c in counts)
             if plan is not None:
                 plan.record_flag(skip)
-            if skip:
-                return x                                # the top-k keeps every row: pruning is the identity
-            interpolated = S.interpolate(scores, x.C)
-            # radix-select keep-mask instead of torch.topk's sort (same row set; ties by index)
-            kept = [min(c, self.pts_threshold) for c in counts]
-            if len(counts) == 1:
-                mask = S.topk_mask(interpolated, self.pts_threshold)
-            else:                                       # per scene: the other scenes' rows are masked to -inf
-                flat, scene = interpolated.view(-1), x.C[:, 0]
-                low = torch.full_like(flat, float("-inf"))
-                mask = None
-                for b, nb in enumerate(counts):
-                    mine = scene == b
-                    m = mine.to(torch.uint8) if nb <= self.pts_threshold else \
-                        S.topk_mask(torch.where(mine, flat, low), self.pts_threshold)
-                    mask = m if mask is None else mask | m
-        return S.prune(x, mask, n_keep=sum(kept), counts=kept)      # the mask holds exactly min(n, threshold) rows per scene
+        if skip:
+            return x                                 # the top-k keeps every row: pruning is the identity
+        mask = self._keep_mask(x, scores, counts)
+        if static:
+            return S.prune(x, mask, n_keep=min(B * T, x.cs.n))
+        kept = [min(c, T) for c in counts]           # the mask holds exactly min(n, threshold) rows per scene
+        return S.prune(x, mask, n_keep=sum(kept), counts=kept)
+
+    @torch.no_grad()
+    def _keep_mask(self, x, scores, counts=None):
+        """uint8 keep-mask of the pruning step: per scene the min(n, pts_threshold) rows of x with the largest interpolated score;
+        of rows with equal scores those with the smaller row index stay (the reference's topk(sorted=False) leaves the choice
+        open).  A radix select (S.topk_mask) instead of torch.topk's sort, under the live-count word x.cs.n_dev (None in the
+        eager forms; rows behind it are never kept).  Several scenes: one select per scene with the other scenes' rows ranked
+        -inf.  counts (host rows per scene, eager forms): a scene at or below the threshold keeps its rows without a select."""
+        T, n_dev = self.pts_threshold, x.cs.n_dev
+        interpolated = S.interpolate(scores, x.C, n_dev)
+        if x.cs.n_batch <= 1:
+            return S.topk_mask(interpolated, T, n_dev=n_dev)         # keeps every row when n <= threshold
+        flat, scene = interpolated.view(-1), x.C[:, 0]
+        low = torch.full_like(flat, float("-inf"))
+        mask = None
+        for b in range(x.cs.n_batch):
+            mine = scene == b
+            if counts is not None and counts[b] <= T:
+                m = mine.to(torch.uint8)
+            else:
+                m = S.topk_mask(torch.where(mine, flat, low), T, n_dev=n_dev)
+                if counts is None:                   # the scene may hold fewer rows than the threshold: the select then also
+                    m = m & mine.to(torch.uint8)     # keeps rows ranked -inf, which are the other scenes'
+            mask = m if mask is None else mask | m
+        return mask
 
     def _head_weights(self):
         """the three 1x1 head convolutions as ONE [128, 1+R+n_cls] GEMM (+ bias row for the class logits)"""
@@ -313,20 +329,31 @@ class FCAF3DHead(nn.Module):
                                                 0.5 * torch.atan2(b[:, 6], b[:, 7])), -1)), dim=-1)
         return S.decode_boxes(points.float(), bbox_pred, self.yaw_parametrization)
 
+    @property
+    def nms_pre(self):
+        """rows per scene and level that the pre-NMS cut lets through (0, also for a missing test config or key: no cut)"""
+        return (self.test_cfg.nms_pre or 0) if self.test_cfg is not None else 0
+
+    @staticmethod
+    def _fused_levels(*lists):
+        """level by level, the single entries of the output lists of forward(..., fused=True)"""
+        for level in zip(*lists):
+            yield [entries[0] for entries in level]
+
+    def _decode_into(self, boxes, scores, ids, cls, cen, box, pts):
+        """boxes and class scores of the rows `ids` (None: every row) of one level, appended to the two lists"""
+        bx, sc = S.select_decode(ids, cls, cen, box, pts, self.yaw_parametrization)
+        boxes.append(bx)
+        scores.append(sc)
+
     def _get_bboxes_single(self, centernesses, bbox_preds, cls_scores, points, scene_id=None, save_path=None):
+        """one scene's levels through the cut (_cut_ids) and the decode; under a recording plan one flag per level: was it cut?"""
         mlvl_bboxes, mlvl_scores = [], []
-        nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
-        plan = P.current()
+        plan, nms_pre = P.current(), self.nms_pre
         for centerness, bbox_pred, cls_score, point in zip(centernesses, bbox_preds, cls_scores, points):
-            ids = None
             if plan is not None:
                 plan.record_flag(len(cls_score) > nms_pre > 0)
-            if len(cls_score) > nms_pre > 0:
-                max_scores = S.max_scores(cls_score, centerness)                            # :249-250 (ranking key only)
-                ids = S.topk_indices(max_scores, nms_pre)                                   # :252-256
-            boxes, scores = S.select_decode(ids, cls_score, centerness, bbox_pred, point, self.yaw_parametrization)
-            mlvl_bboxes.append(boxes)
-            mlvl_scores.append(scores)
+            self._decode_into(mlvl_bboxes, mlvl_scores, _cut_ids(cls_score, centerness, nms_pre), cls_score, centerness, bbox_pred, point)
         bboxes, scores = torch.cat(mlvl_bboxes), torch.cat(mlvl_scores)
         if save_path is not None:
             save_place = os.path.join(save_path, scene_id)
@@ -336,72 +363,58 @@ class FCAF3DHead(nn.Module):
         return bboxes, scores
 
     def get_bboxes(self, centernesses, bbox_preds, cls_scores, points, scene_ids, save_path):
-        out = []
-        for i in range(len(centernesses[0])):
-            out.append(self._get_bboxes_single([x[i] for x in centernesses], [x[i] for x in bbox_preds],
-                                               [x[i] for x in cls_scores], [x[i] for x in points],
-                                               scene_ids[i] if scene_ids is not None else None, save_path))
-        return out
+        return [self.get_bboxes_scene(centernesses, bbox_preds, cls_scores, points, i,
+                                      scene_ids[i] if scene_ids is not None else None, save_path)
+                for i in range(len(centernesses[0]))]
+
+    def get_bboxes_scene(self, centernesses, bbox_preds, cls_scores, points, i=0, scene_id=None, save_path=None):
+        """_get_bboxes_single on scene i of the head's output lists (per level a list with one entry per scene)"""
+        return self._get_bboxes_single(*([x[i] for x in level_lists] for level_lists in (centernesses, bbox_preds, cls_scores, points)),
+                                       scene_id, save_path)
 
     def get_bboxes_static(self, centernesses, bbox_preds, cls_scores, points, coord_sets):
         """_get_bboxes_single inside the static trace (plan.Plan; one scene, forward(..., fused=True) outputs): no row
-        count is read back.  Per level the branch of the calibration run is replayed -- more rows than nms_pre: the
-        nms_pre best by max class score x centerness (dead rows ranked -inf), else all rows -- and its premise registered.
-        Returns (bboxes [K,6|7], scores [K,n_cls], valid int32 [L], sizes): level l owns rows [sum(sizes[:l]), +sizes[l]) of
-        which the first valid[l] are detections.  Order within a level, as in the reference: a level that is cut gives its
-        nms_pre best rows, best first, equal scores by ascending row index (torch.topk leaves ties open); a level that is not
-        gives its live rows in row order.  Flag True: sizes[l] = nms_pre, valid[l] = min(n, nms_pre), premise n > nms_pre.  Flag
-        False (and nms_pre <= 0): sizes[l] = the capacity, valid[l] = n, premise n <= nms_pre.  Flag None on a capacity above
-        nms_pre: the cut form whatever n is -- the one deviation from the reference's order: n <= nms_pre live rows come best
-        first instead of in row order (the same row set, valid[l] = n).  tests/test_head_select_gpu.py pins all of this."""
-        plan = P.current()
-        nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
+        count is read back.  Per level the branch of the calibration run is replayed -- cut (_cut_ids under the live-count
+        word) or all rows -- and its premise registered.  Returns (bboxes [K,6|7], scores [K,n_cls], valid int32 [L], sizes):
+        level l owns rows [sum(sizes[:l]), +sizes[l]) of which the first valid[l] are detections, in the order of _cut_ids.
+        Flag True: sizes[l] = nms_pre, valid[l] = min(n, nms_pre), premise n > nms_pre.  Flag False (and nms_pre <= 0): sizes[l]
+        = the capacity, valid[l] = n, premise n <= nms_pre.  Flag None (the calibration scenes disagreed) on a capacity above
+        nms_pre: the cut form, which is valid on both sides -- the one deviation from the reference's order: n <= nms_pre live
+        rows come best first instead of in row order (the same row set, valid[l] = n).  tests/test_head_select_gpu.py."""
+        plan, nms_pre = P.current(), self.nms_pre
         boxes, scores, valid, sizes = [], [], [], []
-        for cen, box, cls, pts, cs in zip(centernesses, bbox_preds, cls_scores, points, coord_sets):
-            cen, box, cls, pts, cs = cen[0], box[0], cls[0], pts[0], cs[0]
+        for cen, box, cls, pts, cs in self._fused_levels(centernesses, bbox_preds, cls_scores, points, coord_sets):
             cap, n_dev = cs.n, cs.n_dev
             flag = plan.next_flag()
             if flag or (flag is None and cap > nms_pre > 0):
-                # None: the calibration scenes disagreed -- the top-k form is valid on both sides (all live rows when
-                # there are fewer than nms_pre, then in score order instead of row order)
                 assert cap > nms_pre
                 plan.watch(n_dev, nms_pre + 1 if flag else 0, cap)
-                ids = S.topk_indices(S.max_scores(cls, cen), nms_pre, n_dev)
-                k = nms_pre
+                ids, k = _cut_ids(cls, cen, nms_pre, n_dev), nms_pre
                 valid.append(torch.clamp(n_dev.view(1), max=nms_pre).to(torch.int32))
             else:
                 plan.watch(n_dev, 0, min(cap, nms_pre) if nms_pre > 0 else cap)
                 ids, k = None, cap
                 valid.append(n_dev.view(1))
-            bx, sc = S.select_decode(ids, cls, cen, box, pts, self.yaw_parametrization)
-            boxes.append(bx)
-            scores.append(sc)
+            self._decode_into(boxes, scores, ids, cls, cen, box, pts)
             sizes.append(k)
         return torch.cat(boxes), torch.cat(scores), torch.cat(valid), sizes
 
     def get_bboxes_static_multi(self, centernesses, bbox_preds, cls_scores, points, coord_sets, n_scenes):
-        """get_bboxes_static for several scenes in one row set per level (static trace of pipeline.StaticBatch).  Per level
-        and scene: the rows of the other scenes are ranked -inf, the nms_pre best are taken with the radix select; a scene
-        with no more than nms_pre rows on the level keeps them all, in row order like the reference (:247-256 only cuts
-        when there are more).  Returns (bboxes [B,K,6|7], scores [B,K,n_cls], valid int32 [B,L], sizes): scene b / level l
-        owns rows [sum(sizes[:l]), +sizes[l]) of block b, of which the first valid[b,l] are detections."""
-        plan = P.current()
-        nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
-        B = n_scenes
+        """get_bboxes_static for several scenes in one row set per level (static trace of pipeline.StaticBatch): per level ONE
+        sort (_rank_by_scene, dead rows behind every scene), each scene's run found through the device-side offsets; B radix
+        selects per level cost 4x as much.  The plan's flags (the single-scene branches of the calibration) are consumed and not
+        needed.  Returns (bboxes [B,K,6|7], scores [B,K,n_cls], valid int32 [B,L], sizes): scene b / level l owns rows
+        [sum(sizes[:l]), +sizes[l]) of block b, of which the first valid[b,l] are detections, in the order of _cut_ids."""
+        plan, nms_pre, B = P.current(), self.nms_pre, n_scenes
         boxes, scores, valid, sizes = [[] for _ in range(B)], [[] for _ in range(B)], [[] for _ in range(B)], []
-        for cen, box, cls, pts, cs in zip(centernesses, bbox_preds, cls_scores, points, coord_sets):
-            cen, box, cls, pts, cs = cen[0], box[0], cls[0], pts[0], cs[0]
-            plan.next_flag()                                     # the single-scene branch of the calibration: not needed here
+        for cen, box, cls, pts, cs in self._fused_levels(centernesses, bbox_preds, cls_scores, points, coord_sets):
+            plan.next_flag()
             cap, n_dev = cs.n, cs.n_dev
             k = min(nms_pre, cap) if nms_pre > 0 else cap
             cnt, _ = cs.counts_dev()
             ms = S.max_scores(cls, cen)
             live = torch.arange(cap, device=ms.device, dtype=torch.int32) < n_dev
-            # ONE stable sort per level on the key (scene, descending score) -- scores are >= 0, so their bit patterns order
-            # them; dead rows sort behind every scene --: each scene's rows become a contiguous run in rank order, found
-            # through the device-side offsets; B radix selects per level cost 4x as much
-            scene = torch.where(live, cs.C[:, 0], torch.full_like(cs.C[:, 0], B)).long()
-            order = torch.sort((scene << 32) | (0xFFFFFFFF - ms.view(torch.int32).long()), stable=True)[1]
+            order = _rank_by_scene(torch.where(live, cs.C[:, 0], torch.full_like(cs.C[:, 0], B)), ms)
             off = torch.cumsum(cnt, 0) - cnt
             slot = plan.const(lambda: torch.arange(k, device=ms.device, dtype=torch.int64))
             big = plan.const(lambda: torch.full((k,), cap, device=ms.device, dtype=torch.int64))
@@ -410,47 +423,30 @@ class FCAF3DHead(nn.Module):
                 nb = torch.clamp(cnt[b:b + 1], max=k)
                 asc = torch.sort(torch.where(slot < nb, ids, big))[0].clamp_(max=cap - 1)         # the same rows in row order
                 ids = torch.where(cnt[b:b + 1] <= k, asc, ids)
-                bx, sc = S.select_decode(ids, cls, cen, box, pts, self.yaw_parametrization)
-                boxes[b].append(bx)
-                scores[b].append(sc)
+                self._decode_into(boxes[b], scores[b], ids, cls, cen, box, pts)
                 valid[b].append(nb.to(torch.int32))
             sizes.append(k)
         return (torch.stack([torch.cat(x) for x in boxes]), torch.stack([torch.cat(x) for x in scores]),
                 torch.stack([torch.cat(v) for v in valid]), sizes)
 
     def get_bboxes_fused(self, centernesses, bbox_preds, cls_scores, points, scenes, n_scenes):
-        """decode of forward(..., fused=True): per level ONE row set for all scenes + the rows' scene ids.  Per scene the
-        nms_pre best rows by max class score x centerness are picked with the other scenes masked out (reference
-        _get_bboxes_single :247-256 per scene).  Returns [(bboxes, scores)] per scene, the levels concatenated, within a level
-        in the reference's order: a scene with more than nms_pre > 0 rows on the level gives its nms_pre best, best first, equal
-        scores by ascending row index; any other scene gives all its rows in row order (the reference only cuts, and so only
-        reorders, when there are more).  Row for row what _get_bboxes_single gives for that scene alone
-        (tests/test_head_select_gpu.py)."""
-        nms_pre = self.test_cfg.nms_pre if self.test_cfg is not None else 0
-        per_scene = [([], []) for _ in range(n_scenes)]
-        for cen, box, cls, pts, cs in zip(centernesses, bbox_preds, cls_scores, points, scenes):
-            cen, box, cls, pts, cs = cen[0], box[0], cls[0], pts[0], cs[0]
-            sc = cs.C[:, 0]
+        """decode of forward(..., fused=True): per level ONE row set for all scenes + the rows' scene ids.  Returns
+        [(bboxes, scores)] per scene, the levels concatenated: row for row what _get_bboxes_single gives for that scene alone
+        (tests/test_head_select_gpu.py).  One scene: _cut_ids; several: _rank_by_scene, the runs sliced with the host counts.
+        No plan flag is recorded."""
+        nms_pre, per_scene = self.nms_pre, [([], []) for _ in range(n_scenes)]
+        for cen, box, cls, pts, cs in self._fused_levels(centernesses, bbox_preds, cls_scores, points, scenes):
             if n_scenes == 1:
-                ids = None
-                if len(cls) > nms_pre > 0:
-                    ids = S.topk_indices(S.max_scores(cls, cen), nms_pre)
-                groups = [ids]
+                groups = [_cut_ids(cls, cen, nms_pre)]
             else:
-                # ONE stable sort per level on the key (scene, descending score): every scene's rows become a contiguous
-                # run in rank order, of which the first nms_pre are taken (scores are >= 0: their bit patterns order them);
-                # a scene that is not cut gives its whole run, put back into row order
                 counts = cs.batch_counts()                  # usually cached by the pruning step of the same level
-                bits = S.max_scores(cls, cen).view(torch.int32).long()
-                order = torch.sort((sc.long() << 32) | (0xFFFFFFFF - bits), stable=True)[1]
+                order = _rank_by_scene(cs.C[:, 0], S.max_scores(cls, cen))
                 groups, r0 = [], 0
                 for nb in counts:
                     groups.append(order[r0:r0 + nms_pre] if nb > nms_pre > 0 else torch.sort(order[r0:r0 + nb])[0])
                     r0 += nb
             for b, ids in enumerate(groups):
-                bx, scr = S.select_decode(ids, cls, cen, box, pts, self.yaw_parametrization)
-                per_scene[b][0].append(bx)
-                per_scene[b][1].append(scr)
+                self._decode_into(*per_scene[b], ids, cls, cen, box, pts)
         return [(torch.cat(bx), torch.cat(scr)) for bx, scr in per_scene]
 
     def loss(self, centernesses, bbox_preds, cls_scores, points, gt_bboxes, gt_labels):
