@@ -23,6 +23,9 @@ PREP_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_prep.h
 # the evaluation surface (indoor mAP of the detections): include/cnrma_eval.h and its own library, bound the same way
 EVAL_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_eval_hip.so")
 EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_eval.h")
+# the reconstruction-head surface (TSDF regression, fill, loss, backward): include/cnrma_recon.h and its own library, bound the same way
+RECON_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_recon_hip.so")
+RECON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_recon.h")
 # the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
 _CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
@@ -86,6 +89,14 @@ except OSError as e:
 if _eval_exp:
     raise CnrmaError(f"cnrma_eval.h declares experiment entry points ({sorted(_eval_exp)}): the evaluation library has none")
 EVAL_ABI_VERSION = EVAL_CONSTANTS["CNRMA_EVAL_ABI_VERSION"]
+try:
+    with open(RECON_HEADER_PATH) as _f:
+        RECON_SIGNATURES, _recon_exp, RECON_CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {RECON_HEADER_PATH}: {e}") from e
+if _recon_exp:
+    raise CnrmaError(f"cnrma_recon.h declares experiment entry points ({sorted(_recon_exp)}): the reconstruction library has none")
+RECON_ABI_VERSION = RECON_CONSTANTS["CNRMA_RECON_ABI_VERSION"]
 
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
@@ -171,6 +182,36 @@ def call_eval(name, *args):
     rc = getattr(load_eval(), name)(*args)
     if rc != 0:
         raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == EVAL_CONSTANTS["CNRMA_EVAL_EINVAL"]
+                                                          else " (-hipError_t)"))
+    return rc
+
+
+_recon_lib = None
+
+
+def load_recon():
+    """libcnrma_recon_hip.so (include/cnrma_recon.h), loaded once; raises loudly when it is not built"""
+    global _recon_lib
+    if _recon_lib is not None:
+        return _recon_lib
+    if not os.path.exists(RECON_LIB_PATH):
+        raise CnrmaError(f"{RECON_LIB_PATH} not found: build it with `python __graft_entry__.py build` "
+                         f"(or `make -C cn-rma_amd/csrc`). There is no CPU fallback for the product path.")
+    lib = ctypes.CDLL(RECON_LIB_PATH)
+    for name, (res, args) in RECON_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    if lib.cnrma_recon_abi_version() != RECON_ABI_VERSION:
+        raise CnrmaError("ABI version mismatch (libcnrma_recon_hip.so)")
+    _recon_lib = lib
+    return lib
+
+
+def call_recon(name, *args):
+    rc = getattr(load_recon(), name)(*args)
+    if rc != 0:
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == RECON_CONSTANTS["CNRMA_RECON_EINVAL"]
                                                           else " (-hipError_t)"))
     return rc
 

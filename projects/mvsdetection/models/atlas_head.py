@@ -6,6 +6,10 @@ filled with +-0.999 by the previous sign.  Output keys `scene_tsdf_016 / _008 / 
 one is the TSDF the ray marching samples (reference ray_marching.py:486).  Training: L1 in log space on the observed /
 fully-outside voxels, restricted to the sparsified mask from the second scale on.  Parameter names as the reference's
 (`tsdf_head.decoders.{0,1,2}.weight`; reference atlas_head.py:16-81).
+
+`impl="device"` (opt-in; the default "torch" is the code below) runs every scale through cnrma_amd.recon instead: one forward
+launch and two loss launches per scale, feature volumes read in place in fp32 / fp16 / bf16, far voxels never regressed, the
+losses device scalars with no host read.  Same output and loss keys, same gradients.
 """
 import torch
 from torch import nn
@@ -21,8 +25,11 @@ def log_transform(x, shift=1):
 
 @HEADS.register_module()
 class AtlasTSDFHead(nn.Module):
-    def __init__(self, input_channels, n_scales, voxel_size, label_smoothing, sparse_threshold):
+    def __init__(self, input_channels, n_scales, voxel_size, label_smoothing, sparse_threshold, impl="torch"):
         super().__init__()
+        if impl not in ("torch", "device"):
+            raise ValueError(f"AtlasTSDFHead: impl must be 'torch' or 'device', got {impl!r}")
+        self.impl = impl
         self.fp16_enabled = False
         self.input_channels, self.n_scales, self.voxel_size = input_channels, n_scales, voxel_size
         self.label_smoothing, self.sparse_threshold = label_smoothing, sparse_threshold
@@ -31,6 +38,10 @@ class AtlasTSDFHead(nn.Module):
         self.decoders = nn.ModuleList([nn.Conv3d(c, 1, 1, bias=False) for c in list(input_channels)[::-1]])
 
     def forward(self, xs, targets=None):
+        if self.impl == "device":
+            from cnrma_amd import recon
+            return recon.tsdf_head([x.contiguous() for x in xs], [dec.weight for dec in self.decoders], self.sparse_threshold,
+                                   self.label_smoothing, targets, keys=self.keys)
         output, masks = {}, []
         prev = None
         for i, (dec, x) in enumerate(zip(self.decoders, xs)):
