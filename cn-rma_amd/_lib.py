@@ -26,6 +26,9 @@ EVAL_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_eval.h
 # the reconstruction-head surface (TSDF regression, fill, loss, backward): include/cnrma_recon.h and its own library, bound the same way
 RECON_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_recon_hip.so")
 RECON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_recon.h")
+# the 3D U-Net surface (dense 3x3x3 convolutions in f16x3): include/cnrma_unet.h and its own library, bound the same way
+UNET_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_unet_hip.so")
+UNET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_unet.h")
 # the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
 _CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
@@ -97,6 +100,14 @@ except OSError as e:
 if _recon_exp:
     raise CnrmaError(f"cnrma_recon.h declares experiment entry points ({sorted(_recon_exp)}): the reconstruction library has none")
 RECON_ABI_VERSION = RECON_CONSTANTS["CNRMA_RECON_ABI_VERSION"]
+try:
+    with open(UNET_HEADER_PATH) as _f:
+        UNET_SIGNATURES, _unet_exp, UNET_CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {UNET_HEADER_PATH}: {e}") from e
+if _unet_exp:
+    raise CnrmaError(f"cnrma_unet.h declares experiment entry points ({sorted(_unet_exp)}): the 3D U-Net library has none")
+UNET_ABI_VERSION = UNET_CONSTANTS["CNRMA_UNET_ABI_VERSION"]
 
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
@@ -212,6 +223,36 @@ def call_recon(name, *args):
     rc = getattr(load_recon(), name)(*args)
     if rc != 0:
         raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == RECON_CONSTANTS["CNRMA_RECON_EINVAL"]
+                                                          else " (-hipError_t)"))
+    return rc
+
+
+_unet_lib = None
+
+
+def load_unet():
+    """libcnrma_unet_hip.so (include/cnrma_unet.h), loaded once; raises loudly when it is not built"""
+    global _unet_lib
+    if _unet_lib is not None:
+        return _unet_lib
+    if not os.path.exists(UNET_LIB_PATH):
+        raise CnrmaError(f"{UNET_LIB_PATH} not found: build it with `python __graft_entry__.py build` "
+                         f"(or `make -C cn-rma_amd/csrc`). There is no CPU fallback for the product path.")
+    lib = ctypes.CDLL(UNET_LIB_PATH)
+    for name, (res, args) in UNET_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    if lib.cnrma_unet_abi_version() != UNET_ABI_VERSION:
+        raise CnrmaError("ABI version mismatch (libcnrma_unet_hip.so)")
+    _unet_lib = lib
+    return lib
+
+
+def call_unet(name, *args):
+    rc = getattr(load_unet(), name)(*args)
+    if rc != 0:
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == UNET_CONSTANTS["CNRMA_UNET_EINVAL"]
                                                           else " (-hipError_t)"))
     return rc
 

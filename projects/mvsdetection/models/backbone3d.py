@@ -11,6 +11,11 @@ code is written from the architecture description:
   ReLU, then residual blocks.  decoder step i: trilinear x2, 1x1x1 conv to the skip's width, projected skip
   (`proj[i]`: 1x1x1 conv [optionally kept only where the input volume was observed] + norm + ReLU), mean of the two,
   residual blocks.  Returns the decoder features coarse-to-fine.
+
+`impl="device"` (opt-in; the default "torch" is the code path above, untouched) runs every 3x3x3 convolution of an eval-mode,
+no-grad forward through cnrma_amd.unet instead: an implicit GEMM in the project's f16x3 arithmetic with the folded BatchNorm, the
+residual sum and the ReLU in its epilogue.  The 1x1x1 convolutions, the up-sampling and the skip arithmetic stay torch ops.  In
+training mode, or while a gradient is being recorded, the torch path runs.  Same parameter names and state-dict keys.
 """
 import torch
 from torch import nn
@@ -69,8 +74,12 @@ class ConditionalProjection(nn.Module):
 @BACKBONES.register_module()
 class AtlasBackbone3D(nn.Module):
     def __init__(self, channels=(32, 64, 128), layers_down=(1, 2, 3), layers_up=(3, 3, 3), drop=0,
-                 zero_init_residual=True, cond_proj=True, norm="BN"):
+                 zero_init_residual=True, cond_proj=True, norm="BN", impl="torch"):
         super().__init__()
+        if impl not in ("torch", "device"):
+            raise ValueError(f"AtlasBackbone3D: impl must be 'torch' or 'device', got {impl!r}")
+        self.impl = impl
+        self.__dict__["_device_plan"] = None                        # (tag, runners) of the device path; never part of the state
         self.cond_proj = cond_proj
         L = len(channels)
 
@@ -93,12 +102,83 @@ class AtlasBackbone3D(nn.Module):
             for m in self.modules():
                 if isinstance(m, BasicBlock3d):
                     nn.init.constant_(m.bn2.weight, 0)
+        if impl == "device":
+            self._check_device(norm)
+
+    # ---- impl="device": every 3x3x3 convolution, with its eval-mode BatchNorm, the residual sum and the ReLU, runs through
+    # cnrma_amd.unet; the 1x1x1 convolutions, the up-sampling and the skip arithmetic stay torch ops ----
+    def _conv3_layers(self):
+        """(name, conv, norm) of every 3x3x3 convolution, in forward order"""
+        for group, levels in (("layers_down", self.layers_down), ("layers_up_res", self.layers_up_res)):
+            for i, level in enumerate(levels):
+                mods = list(level)
+                if mods and not isinstance(mods[0], BasicBlock3d):
+                    yield f"{group}.{i}.0", mods[0], mods[1]
+                for j, m in enumerate(mods):
+                    if isinstance(m, BasicBlock3d):
+                        yield f"{group}.{i}.{j}.conv1", m.conv1, m.bn1
+                        yield f"{group}.{i}.{j}.conv2", m.conv2, m.bn2
+
+    def _check_device(self, norm):
+        from cnrma_amd import unet
+        if norm != "BN":
+            raise ValueError(f"AtlasBackbone3D: impl='device' folds eval-mode BatchNorm3d and needs norm='BN', got norm={norm!r}")
+        for name, conv, _ in self._conv3_layers():
+            if not unet.widths_supported(conv.in_channels, conv.out_channels):
+                raise ValueError(f"AtlasBackbone3D: impl='device' has no kernel for {name} ({conv.in_channels} -> "
+                                 f"{conv.out_channels} channels): widths must be multiples of 32 up to 256")
+
+    def train(self, mode=True):
+        self.__dict__["_device_plan"] = None          # writes through param.data (EMA hooks) bump no version counter
+        return super().train(mode)
+
+    def _load_from_state_dict(self, *args, **kwargs):
+        self.__dict__["_device_plan"] = None
+        return super()._load_from_state_dict(*args, **kwargs)
+
+    def _device_tag(self):
+        return tuple((t.data_ptr(), t._version) for _, conv, bn in self._conv3_layers()
+                     for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+
+    def _device_runners(self):
+        """weight images and folded BatchNorm constants of every level, made once per set of weights: dropped by train(),
+        load_state_dict() and any in-place update of a parameter or running statistic (version counters)"""
+        from cnrma_amd import unet
+        tag = self._device_tag()
+        plan = self.__dict__["_device_plan"]
+        if plan is None or plan[0] != tag:
+            def level(seq):
+                mods = list(seq)
+                stem = unet.StemRunner(mods[0].weight, mods[1]) if mods and not isinstance(mods[0], BasicBlock3d) else None
+                return stem, [unet.BlockRunner(m.conv1.weight, m.bn1, m.conv2.weight, m.bn2) for m in mods
+                              if isinstance(m, BasicBlock3d)]
+            plan = (tag, [level(s) for s in self.layers_down], [level(s) for s in self.layers_up_res])
+            self.__dict__["_device_plan"] = plan
+        return plan[1], plan[2]
+
+    def _use_device(self, x):
+        if self.impl != "device" or self.training:
+            return False
+        return not (torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())))
+
+    @staticmethod
+    def _run_level(level, x, bound):
+        stem, blocks = level
+        if stem is not None:
+            x, bound = stem(x, bound)
+        for block in blocks:
+            x, bound = block(x, bound)
+        return x, bound
 
     def forward(self, x):
+        device = self._use_device(x)
+        if device:
+            downs, ups = self._device_runners()
+            x = x.contiguous()
         observed = (x != 0).any(1, keepdim=True).float() if self.cond_proj else None
-        skips = []
-        for layer in self.layers_down:
-            x = layer(x)
+        skips, bound = [], None                                     # bound: the magnitude bound the last device layer published
+        for i, layer in enumerate(self.layers_down):
+            x, bound = self._run_level(downs[i], x, bound) if device else (layer(x), None)
             skips.append(x)
         skips.reverse()
         steps = len(self.layers_up_conv)
@@ -108,6 +188,7 @@ class AtlasBackbone3D(nn.Module):
             mask = None
             if self.cond_proj:
                 mask = F.interpolate(observed, scale_factor=1 / 2 ** (steps - i - 1)) != 0
-            x = self.layers_up_res[i]((x + self.proj[i](skips[i + 1], x, mask)) / 2)
+            x = (x + self.proj[i](skips[i + 1], x, mask)) / 2
+            x = self._run_level(ups[i], x, None)[0] if device else self.layers_up_res[i](x)
             out.append(x)
         return out
