@@ -29,6 +29,10 @@ RECON_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_recon
 # the 3D U-Net surface (dense 3x3x3 convolutions in f16x3): include/cnrma_unet.h and its own library, bound the same way
 UNET_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_unet_hip.so")
 UNET_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_unet.h")
+# the 3D U-Net decoder joints (up-sampling, 1x1x1 convolutions, conditional skip and mean in one pass): include/cnrma_unet_join.h and
+# its own library, bound the same way
+UNET_JOIN_LIB_PATH = os.path.join(_HERE, "csrc", "libcnrma_unetjoin_hip.so")
+UNET_JOIN_HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "cnrma_unet_join.h")
 # the header's whole vocabulary: a parameter whose text holds a `*` is a pointer, the scalars by name.  A new one is a line here
 _CTYPES = {"*": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
            "double": ctypes.c_double, "size_t": ctypes.c_size_t, "uint32_t": ctypes.c_uint32}
@@ -108,6 +112,14 @@ except OSError as e:
 if _unet_exp:
     raise CnrmaError(f"cnrma_unet.h declares experiment entry points ({sorted(_unet_exp)}): the 3D U-Net library has none")
 UNET_ABI_VERSION = UNET_CONSTANTS["CNRMA_UNET_ABI_VERSION"]
+try:
+    with open(UNET_JOIN_HEADER_PATH) as _f:
+        UNET_JOIN_SIGNATURES, _unet_join_exp, UNET_JOIN_CONSTANTS = _read_header(_f.read())
+except OSError as e:
+    raise CnrmaError(f"cannot read the C-ABI header {UNET_JOIN_HEADER_PATH}: {e}") from e
+if _unet_join_exp:
+    raise CnrmaError(f"cnrma_unet_join.h declares experiment entry points ({sorted(_unet_join_exp)}): the joint library has none")
+UNET_JOIN_ABI_VERSION = UNET_JOIN_CONSTANTS["CNRMA_UNET_JOIN_ABI_VERSION"]
 
 _libs = {}            # False: product library, True: experiments library
 _active = False       # which of the two load() / call() use
@@ -254,6 +266,36 @@ def call_unet(name, *args):
     if rc != 0:
         raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)" if rc == UNET_CONSTANTS["CNRMA_UNET_EINVAL"]
                                                           else " (-hipError_t)"))
+    return rc
+
+
+_unet_join_lib = None
+
+
+def load_unet_join():
+    """libcnrma_unetjoin_hip.so (include/cnrma_unet_join.h), loaded once; raises loudly when it is not built"""
+    global _unet_join_lib
+    if _unet_join_lib is not None:
+        return _unet_join_lib
+    if not os.path.exists(UNET_JOIN_LIB_PATH):
+        raise CnrmaError(f"{UNET_JOIN_LIB_PATH} not found: build it with `python __graft_entry__.py build` "
+                         f"(or `make -C cn-rma_amd/csrc`). There is no CPU fallback for the product path.")
+    lib = ctypes.CDLL(UNET_JOIN_LIB_PATH)
+    for name, (res, args) in UNET_JOIN_SIGNATURES.items():
+        fn = getattr(lib, name)  # AttributeError if the symbol is missing
+        fn.restype = res
+        fn.argtypes = args
+    if lib.cnrma_unet_join_abi_version() != UNET_JOIN_ABI_VERSION:
+        raise CnrmaError("ABI version mismatch (libcnrma_unetjoin_hip.so)")
+    _unet_join_lib = lib
+    return lib
+
+
+def call_unet_join(name, *args):
+    rc = getattr(load_unet_join(), name)(*args)
+    if rc != 0:
+        raise CnrmaError(f"{name} failed with code {rc}" + (" (invalid argument)"
+                                                          if rc == UNET_JOIN_CONSTANTS["CNRMA_UNET_JOIN_EINVAL"] else " (-hipError_t)"))
     return rc
 
 

@@ -10,11 +10,20 @@ x and y are fp32 contiguous NCDHW; the arithmetic is the project's f16x3 (two fp
 accumulation) with power-of-two scales from device-side magnitude bounds.  A bound is BOUND_WORDS fp32 words on the device (the
 maximum of 64 slots); every convolution publishes its output's bound for the next layer, so a chain of layers needs one `absmax`
 pass, over the network's input.  Nothing is read back and nothing synchronises: the calls run on the current stream and can be
-captured.  Inference only: no autograd."""
+captured.  Inference only: no autograd.
+
+The decoder joints between the convolutions (csrc/unet_join.hip, include/cnrma_unet_join.h; reference backbone3d.py:188-196):
+
+    observed = observed_mask(x)                                            # uint8 [B, X, Y, Z]: any over c of x != 0
+    observed, bound_x = observed_mask(x, with_bound=True)                  # ... and x's magnitude bound from the same pass
+    out, bound_out = join(xc, e, w_up, w_proj, scale, shift, observed=None, step=1)
+    joint = JointRunner(up_conv.weight, proj.conv.weight, proj.norm); out, bound_out = joint(xc, e, observed, step)
+
+out = (u + ReLU(scale * (observed ? p : u) + shift)) / 2 with u = w_up . trilinear_x2(xc) and p = w_proj . e, in exact fp32."""
 import torch
 
 from . import _lib
-from ._lib import CnrmaError, call_unet, ptr, stream
+from ._lib import CnrmaError, call_unet, call_unet_join, ptr, stream
 
 EINVAL = _lib.UNET_CONSTANTS["CNRMA_UNET_EINVAL"]
 BOUND_WORDS = _lib.UNET_CONSTANTS["CNRMA_UNET_BOUND_WORDS"]
@@ -147,3 +156,95 @@ class StemRunner(ConvBN):
 
     def __init__(self, conv_weight, bn):
         super().__init__(conv_weight, bn, stride=2)
+
+
+# ---- the decoder joints: libcnrma_unetjoin_hip.so ----
+def _refuse_join(what):
+    raise CnrmaError(f"join: {what} (invalid argument, {_lib.UNET_JOIN_CONSTANTS['CNRMA_UNET_JOIN_EINVAL']}); nothing was launched")
+
+
+def _volume(t, name):
+    if t.dim() != 5 or t.dtype != torch.float32:
+        _refuse_join(f"{name} must be float32 [B, C, X, Y, Z], got {tuple(t.shape)} of {t.dtype}")
+    if not t.is_contiguous():
+        _refuse_join(f"{name} must be contiguous (shape {tuple(t.shape)}, strides {t.stride()})")
+
+
+def observed_mask(x, with_bound=False):
+    """x [B, C, X, Y, Z] fp32 contiguous -> observed uint8 [B, X, Y, Z] = (x != 0).any(1), read once; with_bound: -> (observed,
+    bound_x), bound_x the magnitude bound of x (what absmax(x) gives) from the same pass"""
+    _lib.require_gpu()
+    _volume(x, "x")
+    B, C, X, Y, Z = x.shape
+    if min(B, C, X, Y, Z) < 1 or B > 65535 or x.numel() >= 2 ** 31:
+        _refuse_join(f"a volume of shape {tuple(x.shape)} is not supported")
+    x = x.detach()
+    observed = torch.empty((B, X, Y, Z), dtype=torch.uint8, device=x.device)
+    bound = torch.empty(BOUND_WORDS, dtype=torch.float32, device=x.device) if with_bound else None
+    call_unet_join("cnrma_unet_join_observed", ptr(x), B, C, X, Y, Z, ptr(observed), ptr(bound), stream())
+    return (observed, bound) if with_bound else observed
+
+
+def join(xc, e, w_up, w_proj, scale, shift, observed=None, step=1, out=None, scratch=None):
+    """one decoder joint.  xc [B, Cc, Xc, Yc, Zc], e [B, Cf, 2Xc, 2Yc, 2Zc], w_up [Cf, Cc] and w_proj [Cf, Cf] (any trailing 1s),
+    scale / shift [Cf] (both None: no affine map), observed: None or uint8 [B, step 2Xc, step 2Yc, step 2Zc] (observed_mask of the
+    network's input), everything fp32 contiguous on one device; out: a tensor like e to write (allocated when None); scratch: a
+    uint8 buffer of cnrma_unet_join_scratch_bytes to reuse (allocated when None).  -> (out, bound_out), bound_out = max|out| in the
+    convention conv3 takes as `bound`."""
+    _lib.require_gpu()
+    _volume(xc, "xc")
+    _volume(e, "e")
+    B, Cc, Xc, Yc, Zc = xc.shape
+    Cf = e.shape[1]
+    if e.shape[0] != B or tuple(e.shape[2:]) != (2 * Xc, 2 * Yc, 2 * Zc) or e.device != xc.device:
+        _refuse_join(f"e must be [B, Cf, 2Xc, 2Yc, 2Zc] on {xc.device} for xc {tuple(xc.shape)}, got {tuple(e.shape)} on {e.device}")
+    if not _lib.load_unet_join().cnrma_unet_join_supported(B, Cc, Cf, Xc, Yc, Zc):
+        _refuse_join(f"a joint {Cc} -> {Cf} over {tuple(xc.shape)} is not supported")
+    for name, w, cin in (("w_up", w_up, Cc), ("w_proj", w_proj, Cf)):
+        if w.dtype != torch.float32 or w.dim() < 2 or tuple(w.shape[:2]) != (Cf, cin) or w.numel() != Cf * cin or w.device != xc.device:
+            _refuse_join(f"{name} must be float32 [{Cf}, {cin}] on {xc.device}, got {tuple(w.shape)} of {w.dtype} on {w.device}")
+        if not w.is_contiguous():
+            _refuse_join(f"{name} must be contiguous (shape {tuple(w.shape)}, strides {w.stride()})")
+    if (scale is None) != (shift is None):
+        _refuse_join("scale and shift come together")
+    if scale is not None:
+        scale, shift = _vector(scale, "scale", Cf, xc.device), _vector(shift, "shift", Cf, xc.device)
+    if observed is not None:
+        if not isinstance(step, int) or step < 1:
+            _refuse_join(f"step must be a positive integer, got {step!r}")
+        want = (B, step * 2 * Xc, step * 2 * Yc, step * 2 * Zc)
+        if observed.dtype != torch.uint8 or tuple(observed.shape) != want or not observed.is_contiguous() or observed.device != xc.device:
+            _refuse_join(f"observed must be contiguous uint8 {want} on {xc.device}, got {tuple(observed.shape)} of {observed.dtype}, "
+                         f"strides {observed.stride()}")
+    if out is not None and (out.dtype != torch.float32 or out.shape != e.shape or not out.is_contiguous() or out.device != xc.device):
+        _refuse_join(f"out must be contiguous float32 {tuple(e.shape)} on {xc.device}, got {tuple(out.shape)} of {out.dtype}, "
+                     f"strides {out.stride()}")
+    nbytes = _lib.load_unet_join().cnrma_unet_join_scratch_bytes(B, Cc, Cf, Xc, Yc, Zc)
+    if scratch is None:
+        scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+    elif scratch.dtype != torch.uint8 or scratch.numel() < nbytes or not scratch.is_contiguous() or scratch.device != xc.device:
+        _refuse_join(f"scratch must hold {nbytes} bytes (uint8) on {xc.device}")
+    y = torch.empty_like(e) if out is None else out
+    bound_out = torch.empty(BOUND_WORDS, dtype=torch.float32, device=xc.device)
+    call_unet_join("cnrma_unet_join_forward", ptr(xc.detach()), ptr(e.detach()), ptr(w_up.detach()), ptr(w_proj.detach()), ptr(scale),
+                   ptr(shift), ptr(observed), int(step), B, Cc, Cf, Xc, Yc, Zc, ptr(scratch), ptr(y), ptr(bound_out), stream())
+    return y, bound_out
+
+
+class JointRunner:
+    """one decoder joint of the module in eval mode: layers_up_conv[i] (1x1x1), proj[i].conv (1x1x1) and proj[i].norm, folded once here.
+    The weights are read as they lie (no prepared image); the scratch of the coarse product is kept between calls of one shape"""
+
+    def __init__(self, up_weight, proj_weight, norm):
+        if norm.running_mean is None or norm.running_var is None:
+            _refuse_join("the BatchNorm keeps no running statistics: there is no eval-mode map to fold")
+        self.w_up, self.w_proj = up_weight.detach().contiguous(), proj_weight.detach().contiguous()
+        self.scale, self.shift = fold_batchnorm(norm.weight, norm.bias, norm.running_mean, norm.running_var, norm.eps)
+        self.scratch = None
+
+    def __call__(self, xc, e, observed=None, step=1):
+        if xc.dim() == 5 and e.dim() == 5:
+            nbytes = _lib.load_unet_join().cnrma_unet_join_scratch_bytes(xc.shape[0], xc.shape[1], e.shape[1], *xc.shape[2:])
+            if self.scratch is None or self.scratch.numel() < nbytes or self.scratch.device != xc.device:
+                self.scratch = torch.empty(nbytes, dtype=torch.uint8, device=xc.device)
+        return join(xc, e, self.w_up, self.w_proj, self.scale, self.shift, observed=observed, step=step, scratch=self.scratch)

@@ -16,6 +16,11 @@ code is written from the architecture description:
 no-grad forward through cnrma_amd.unet instead: an implicit GEMM in the project's f16x3 arithmetic with the folded BatchNorm, the
 residual sum and the ReLU in its epilogue.  The 1x1x1 convolutions, the up-sampling and the skip arithmetic stay torch ops.  In
 training mode, or while a gradient is being recorded, the torch path runs.  Same parameter names and state-dict keys.
+
+`joints="device"` (opt-in, needs impl="device"; the default "torch" is the paragraph above, bit for bit) also runs every decoder joint
+-- up-sampling, both 1x1x1 convolutions, the conditional skip, its BatchNorm and ReLU, and the mean -- as one fused pass of
+cnrma_amd.unet.join in exact fp32, and takes the observed mask and the input's magnitude bound from one pass over the input.  Each
+joint publishes its output's bound, so the device forward measures no magnitude after the input's.
 """
 import torch
 from torch import nn
@@ -74,11 +79,15 @@ class ConditionalProjection(nn.Module):
 @BACKBONES.register_module()
 class AtlasBackbone3D(nn.Module):
     def __init__(self, channels=(32, 64, 128), layers_down=(1, 2, 3), layers_up=(3, 3, 3), drop=0,
-                 zero_init_residual=True, cond_proj=True, norm="BN", impl="torch"):
+                 zero_init_residual=True, cond_proj=True, norm="BN", impl="torch", joints="torch"):
         super().__init__()
         if impl not in ("torch", "device"):
             raise ValueError(f"AtlasBackbone3D: impl must be 'torch' or 'device', got {impl!r}")
-        self.impl = impl
+        if joints not in ("torch", "device"):
+            raise ValueError(f"AtlasBackbone3D: joints must be 'torch' or 'device', got {joints!r}")
+        if joints == "device" and impl != "device":
+            raise ValueError(f"AtlasBackbone3D: joints='device' needs impl='device', got impl={impl!r}")
+        self.impl, self.joints = impl, joints
         self.__dict__["_device_plan"] = None                        # (tag, runners) of the device path; never part of the state
         self.cond_proj = cond_proj
         L = len(channels)
@@ -104,9 +113,11 @@ class AtlasBackbone3D(nn.Module):
                     nn.init.constant_(m.bn2.weight, 0)
         if impl == "device":
             self._check_device(norm)
+        if joints == "device":
+            self._check_joints(norm)
 
     # ---- impl="device": every 3x3x3 convolution, with its eval-mode BatchNorm, the residual sum and the ReLU, runs through
-    # cnrma_amd.unet; the 1x1x1 convolutions, the up-sampling and the skip arithmetic stay torch ops ----
+    # cnrma_amd.unet; the 1x1x1 convolutions, the up-sampling and the skip arithmetic stay torch ops unless joints="device" ----
     def _conv3_layers(self):
         """(name, conv, norm) of every 3x3x3 convolution, in forward order"""
         for group, levels in (("layers_down", self.layers_down), ("layers_up_res", self.layers_up_res)):
@@ -128,6 +139,16 @@ class AtlasBackbone3D(nn.Module):
                 raise ValueError(f"AtlasBackbone3D: impl='device' has no kernel for {name} ({conv.in_channels} -> "
                                  f"{conv.out_channels} channels): widths must be multiples of 32 up to 256")
 
+    def _check_joints(self, norm):
+        from cnrma_amd import unet
+        if norm != "BN":
+            raise ValueError(f"AtlasBackbone3D: joints='device' folds eval-mode BatchNorm3d and needs norm='BN', got norm={norm!r}")
+        for i, (up, proj) in enumerate(zip(self.layers_up_conv, self.proj)):
+            for name, conv in ((f"layers_up_conv.{i}", up), (f"proj.{i}.conv", proj.conv)):
+                if not unet.widths_supported(conv.in_channels, conv.out_channels):
+                    raise ValueError(f"AtlasBackbone3D: joints='device' has no kernel for {name} ({conv.in_channels} -> "
+                                     f"{conv.out_channels} channels): widths must be multiples of 32 up to 256")
+
     def train(self, mode=True):
         self.__dict__["_device_plan"] = None          # writes through param.data (EMA hooks) bump no version counter
         return super().train(mode)
@@ -137,8 +158,13 @@ class AtlasBackbone3D(nn.Module):
         return super()._load_from_state_dict(*args, **kwargs)
 
     def _device_tag(self):
-        return tuple((t.data_ptr(), t._version) for _, conv, bn in self._conv3_layers()
-                     for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        tag = tuple((t.data_ptr(), t._version) for _, conv, bn in self._conv3_layers()
+                    for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+        if self.joints == "device":
+            tag += tuple((t.data_ptr(), t._version) for up, proj in zip(self.layers_up_conv, self.proj)
+                         for t in (up.weight, proj.conv.weight, proj.norm.weight, proj.norm.bias, proj.norm.running_mean,
+                                   proj.norm.running_var))
+        return tag
 
     def _device_runners(self):
         """weight images and folded BatchNorm constants of every level, made once per set of weights: dropped by train(),
@@ -152,9 +178,12 @@ class AtlasBackbone3D(nn.Module):
                 stem = unet.StemRunner(mods[0].weight, mods[1]) if mods and not isinstance(mods[0], BasicBlock3d) else None
                 return stem, [unet.BlockRunner(m.conv1.weight, m.bn1, m.conv2.weight, m.bn2) for m in mods
                               if isinstance(m, BasicBlock3d)]
-            plan = (tag, [level(s) for s in self.layers_down], [level(s) for s in self.layers_up_res])
+            joints = None
+            if self.joints == "device":
+                joints = [unet.JointRunner(up.weight, proj.conv.weight, proj.norm) for up, proj in zip(self.layers_up_conv, self.proj)]
+            plan = (tag, [level(s) for s in self.layers_down], [level(s) for s in self.layers_up_res], joints)
             self.__dict__["_device_plan"] = plan
-        return plan[1], plan[2]
+        return plan[1], plan[2], plan[3]
 
     def _use_device(self, x):
         if self.impl != "device" or self.training:
@@ -172,11 +201,16 @@ class AtlasBackbone3D(nn.Module):
 
     def forward(self, x):
         device = self._use_device(x)
+        joints, bound = None, None                                  # bound: the magnitude bound the last device layer published
         if device:
-            downs, ups = self._device_runners()
+            downs, ups, joints = self._device_runners()
             x = x.contiguous()
-        observed = (x != 0).any(1, keepdim=True).float() if self.cond_proj else None
-        skips, bound = [], None                                     # bound: the magnitude bound the last device layer published
+        if joints is None:
+            observed = (x != 0).any(1, keepdim=True).float() if self.cond_proj else None
+        else:                                                       # one pass over the input: the mask and the first layer's bound
+            from cnrma_amd import unet
+            observed, bound = unet.observed_mask(x, with_bound=True) if self.cond_proj else (None, None)
+        skips = []
         for i, layer in enumerate(self.layers_down):
             x, bound = self._run_level(downs[i], x, bound) if device else (layer(x), None)
             skips.append(x)
@@ -184,6 +218,11 @@ class AtlasBackbone3D(nn.Module):
         steps = len(self.layers_up_conv)
         out = []
         for i in range(steps):
+            if joints is not None:                                  # the whole joint in one fused pass; its bound feeds the level
+                x, bound = joints[i](x, skips[i + 1], observed, 2 ** (steps - i - 1))
+                x = self._run_level(ups[i], x, bound)[0]
+                out.append(x)
+                continue
             x = self.layers_up_conv[i](F.interpolate(x, scale_factor=2, mode="trilinear", align_corners=False))
             mask = None
             if self.cond_proj:
