@@ -55,16 +55,26 @@ __device__ __forceinline__ float read_amax(const float* slots) {            // e
   return wave_max(slots[(threadIdx.x & 63) * AMAX_STRIDE]);
 }
 
-// v >= 0 (uint order == float order); blockDim.x == 256, every thread of the block calls it; sh4: 4 floats of LDS
-__device__ __forceinline__ void block_amax_publish(float* slots, float v, float* sh4) {
+// one thread hands in its block's candidate m >= 0 (uint order == float order)
+__device__ __forceinline__ void amax_publish_candidate(float* slots, float m) {
+  const unsigned slot = (blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) & (AMAX_SLOTS - 1);
+  unsigned* d = reinterpret_cast<unsigned*>(slots + slot * AMAX_STRIDE);
+  const unsigned bits = __float_as_uint(m);
+  if (bits > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, bits);
+}
+
+// v >= 0; blockDim.x == 64 * WAVES, every thread of the block calls it; sh: WAVES floats of LDS
+template <int WAVES = 4>
+__device__ __forceinline__ void block_amax_publish(float* slots, float v, float* sh) {
   v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
   __syncthreads();
   if (threadIdx.x == 0) {
-    const float m = fmaxf(fmaxf(sh4[0], sh4[1]), fmaxf(sh4[2], sh4[3]));
-    const unsigned slot = (blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) & (AMAX_SLOTS - 1);
-    unsigned* d = reinterpret_cast<unsigned*>(slots + slot * AMAX_STRIDE);
-    const unsigned bits = __float_as_uint(m);
-    if (bits > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, bits);
+    // by pairs, not in sequence: the order is free (a maximum of non-negative values), and this one keeps the instruction
+    // streams of the 256-thread callers, the sparse family's kernels, what they were
+    float m = WAVES > 1 ? fmaxf(sh[0], sh[1]) : sh[0];
+#pragma unroll
+    for (int w = 2; w < WAVES; w += 2) m = fmaxf(m, w + 1 < WAVES ? fmaxf(sh[w], sh[w + 1]) : sh[w]);
+    amax_publish_candidate(slots, m);
   }
 }

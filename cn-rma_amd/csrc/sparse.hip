@@ -418,6 +418,107 @@ __device__ __forceinline__ void store_split(uint16_t* sp, int64_t row, int C, in
   q[0] = h; q[8] = m; q[16] = l;
 }
 
+// ---- the epilogue of the family, stated once ---------------------------------------------------------------------------------
+// out = act(sum * out_scale * scale[col] + shift[col] + residual[row][col]), every step a statement of its own and in this order:
+// the numerical contract of the family.  The kernel forms are bit-identical to each other because they share it, and a split
+// launch equals an unsplit one because conv_reduce_kernel applies it to the same sums.  (-ffp-contract=off keeps the multiply
+// and the add apart.)  A caller names the steps it performs: constants in the tile kernels, runtime tests in the reducers.
+struct EpiSteps { bool out_scale, scale, shift, residual; };
+
+__device__ __forceinline__ float epilogue_value(EpiSteps on, float v, float out_scale, float sc, float sh, float res, int act) {
+  if (on.out_scale) v = v * out_scale;                      // undo the f16x3 operand scales (a power of two)
+  if (on.scale) v = v * sc;
+  if (on.shift) v = v + sh;
+  if (on.residual) v = v + res;
+  return apply_act(v, act);
+}
+
+// A wave's 32x32 accumulator tile in the D layout of the 32x32 MFMAs: element i of lane l is column l & 31, row
+// (i & 3) + 8 * (i >> 2) + 4 * (l >> 5).  EpiCol: the lane's column; row0 below: the tile's first row + 4 * (lane >> 5).
+struct EpiCol { int col; bool ok; int colc; float sc, sh; };   // colc: clamped (a valid address); sc = 1, sh = 0 where absent
+// where finished rows go: tile row r is row r * row_step + child of dst and of the residual (the stage kernels' generative
+// transpose; 1, 0 elsewhere)
+struct EpiOut {
+  float* dst; const float* residual; int act; int Cout; int64_t n_live;
+  int row_step = 1, child = 0;
+};
+struct EpiKeepAll { __device__ bool operator()(float) const { return true; } };
+
+__device__ __forceinline__ EpiCol epi_col(const ConvArgs& p, int col, bool use_scale, bool use_shift) {
+  const bool ok = col < p.Cout;
+  const int colc = ok ? col : 0;
+  return {col, ok, colc, use_scale ? p.scale[colc] : 1.0f, use_shift ? p.shift[colc] : 0.0f};
+}
+
+// one tile -> finished rows, four rows at a time (short live ranges): the residual loads of a group leave before its arithmetic,
+// with the row clamped (branch-free), and every value is one predicated store.  SCALED: the kernel multiplies by out_scale;
+// HAS_RES: it adds the residual; TRACK_MX: mx follows max|v| of the lane's stored values (the f16x3 consumers' bound).
+// sparse_conv_bf16x6_kernel keeps this loop nest in its own body (see there): it alone writes the split companion
+template <bool SCALED, bool HAS_RES, bool TRACK_MX, class Keep = EpiKeepAll>
+__device__ __forceinline__ void epilogue_tile(const f32x16& acc, int64_t row0, const EpiCol& c, float out_scale, const EpiOut& o,
+                                              float& mx, Keep keep = Keep()) {
+#pragma unroll
+  for (int rg = 0; rg < 4; ++rg) {
+    float res[4];
+    if constexpr (HAS_RES) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const int64_t row = row0 + q + 8 * rg;
+        const int64_t rc = row < o.n_live ? row : o.n_live - 1;
+        res[q] = o.residual[(rc * o.row_step + o.child) * o.Cout + c.colc];
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int64_t row = row0 + q + 8 * rg;
+      const float v = epilogue_value({SCALED, true, true, HAS_RES}, acc[rg * 4 + q], out_scale, c.sc, c.sh,
+                                     HAS_RES ? res[q] : 0.0f, o.act);
+      if (c.ok && row < o.n_live && keep(v)) {
+        o.dst[(row * o.row_step + o.child) * o.Cout + c.col] = v;
+        if constexpr (TRACK_MX) mx = fmaxf(mx, fabsf(v));
+      }
+    }
+  }
+}
+
+// the exact-fp32 kernels: no bound to publish, nothing tracked
+template <bool SCALED, bool HAS_RES>
+__device__ __forceinline__ void epilogue_tile(const f32x16& acc, int64_t row0, const EpiCol& c, float out_scale, const EpiOut& o) {
+  float untracked = 0.0f;
+  epilogue_tile<SCALED, HAS_RES, false>(acc, row0, c, out_scale, o, untracked);
+}
+
+// one tile -> a split's slab: raw partial sums (times out_scale where the kernel has one); a reduction follows
+template <bool SCALED>
+__device__ __forceinline__ void slab_tile(const f32x16& acc, int64_t row0, int col, bool col_ok, float out_scale, float* slab,
+                                          int Cout, int64_t n_live) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) {
+    const int64_t row = row0 + (i & 3) + 8 * (i >> 2);
+    if (col_ok && row < n_live) slab[row * Cout + col] = SCALED ? acc[i] * out_scale : acc[i];
+  }
+}
+
+// KS == 2 of the gather-once kernels: the two offset halves of a 64-row tile meet.  Each wave hands the row tile it does not
+// finish to its partner through X (4 x 4 KB of LDS that nobody reads any more) and finishes the other: wave (kg, wc) ends up
+// with rows 32 * kg .. + 31 of columns 32 * wc .. + 31 in acc_kg.  Every wave of the block calls it
+__device__ __forceinline__ void merge_offset_halves(f32x16& acc0, f32x16& acc1, float* X, int wc, int kg, int lane) {
+  __syncthreads();
+  float* mine = X + (wc * 2 + kg) * 1024;
+  const float* theirs = X + (wc * 2 + (kg ^ 1)) * 1024;
+  auto give = [&](const f32x16& a) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = a[i];
+  };
+  auto take = [&](f32x16& a) {
+#pragma unroll
+    for (int i = 0; i < 16; ++i) a[i] += theirs[i * 64 + lane];
+  };
+  if (kg == 0) give(acc1); else give(acc0);                 // (a branch per wave: a select would cost 16 VALU per tile)
+  __syncthreads();
+  if (kg == 0) take(acc0); else take(acc1);
+}
+
 // FAST: Cin % 32 == 0 and Cout % 4 == 0 and Cout >= 4 -- every staging load is an unconditional 16-byte load with
 // a clamped address and a select afterwards (no per-element branches: hipcc would wait vmcnt(0) inside each one and
 // serialise the whole prefetch).
@@ -607,45 +708,17 @@ __global__ __launch_bounds__(256) void sparse_conv_mfma_kernel(ConvArgs p) {
     cin0 = ncin;
   }
 
-  // ---- epilogue.  D layout: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
+  // ---- epilogue: exact fp32, so no operand scale to undo and no bound to publish.  A split launch sends its raw sums to its
+  // slab through the same chain (scale 1, shift 0, no activation)
   const bool partial = p.splits > 1;
-  float* dst = partial ? p.slab + (int64_t)zs * p.no_cap * Cout : p.out;
-  const int child = p.slices > 1 ? morton_child(zs) : 0, row_step = p.slices > 1 ? p.slices : 1;   // see slice_out_row()
   const bool use_scale = !partial && p.scale != nullptr, use_shift = !partial && p.shift != nullptr;
-  const int act = partial ? 0 : p.act;
+  EpiOut o{partial ? p.slab + (int64_t)zs * p.no_cap * Cout : p.out, p.residual, partial ? 0 : p.act, Cout, n_live};
+  if (p.slices > 1) { o.row_step = p.slices; o.child = morton_child(zs); }                         // see slice_out_row()
 #pragma unroll
   for (int b = 0; b < TN; ++b) {
-    const int col = cout0 + wc * (32 * TN) + b * 32 + (lane & 31);
-    const bool col_ok = col < Cout;
-    const int colc = col_ok ? col : 0;
-    const float sc = use_scale ? p.scale[colc] : 1.0f;
-    const float sh = use_shift ? p.shift[colc] : 0.0f;
+    const EpiCol c = epi_col(p, cout0 + wc * (32 * TN) + b * 32 + (lane & 31), use_scale, use_shift);
 #pragma unroll
-    for (int a = 0; a < TM; ++a) {
-      const int64_t row0 = tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {                                 // 4 rows at a time: short live ranges
-        float res[4];
-        if constexpr (HAS_RES) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t row = row0 + q + 8 * rg;
-            const int64_t rc = row < n_live ? row : n_live - 1;        // clamped, branch-free
-            res[q] = p.residual[(rc * row_step + child) * Cout + colc];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t row = row0 + q + 8 * rg;
-          float v = acc[a][b][rg * 4 + q];
-          v = v * sc;
-          v = v + sh;
-          if constexpr (HAS_RES) v = v + res[q];
-          v = apply_act(v, act);
-          if (col_ok && row < n_live) dst[(row * row_step + child) * Cout + col] = v;
-        }
-      }
-    }
+    for (int a = 0; a < TM; ++a) epilogue_tile<false, HAS_RES>(acc[a][b], tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5), c, 1.0f, o);
   }
 }
 
@@ -1136,6 +1209,8 @@ __global__ __launch_bounds__(256, 2) void sparse_conv_bf16x6_kernel(ConvArgs p, 
   if (p.out_split && p.splits <= 1 && blockIdx.x == 0 && blockIdx.y == 0 && zs == 0) {
     for (int i = tid; i < (Cout >> 3) * 24; i += 256) p.out_split[p.out_zero_row * (Cout >> 3) * 24 + i] = 0;
   }
+  // ---- epilogue: epilogue_tile()'s loop nest, written out.  This kernel alone writes the split companion, and its four waves
+  // per SIMD at TN = 2 need every tile's address arithmetic to stay its own (profiles/conv_epilogue_resources.md)
   const bool partial = p.splits > 1;
   float* dst = partial ? p.slab + (int64_t)zs * p.no_cap * Cout : p.out;
   const int child = p.slices > 1 ? morton_child(zs) : 0, row_step = p.slices > 1 ? p.slices : 1;   // see slice_out_row()
@@ -1166,12 +1241,8 @@ __global__ __launch_bounds__(256, 2) void sparse_conv_bf16x6_kernel(ConvArgs p, 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const int64_t row = row0 + q + 8 * rg;
-          float v = acc[a][b][rg * 4 + q];
-          if constexpr (MODE == 1) v = v * out_scale;                  // undo the operand scales (a power of two)
-          v = v * sc;
-          v = v + sh;
-          if constexpr (HAS_RES) v = v + res[q];
-          v = apply_act(v, act);
+          const float v = epilogue_value({MODE == 1, true, true, HAS_RES}, acc[a][b][rg * 4 + q], out_scale, sc, sh,
+                                         HAS_RES ? res[q] : 0.0f, act);   // only f16x3 (MODE 1) has operand scales to undo
           if (col_ok && row < n_live) {
             dst[(row * row_step + child) * Cout + col] = v;
             if (!partial && p.out_split) store_split(p.out_split, row * row_step + child, Cout, col, v);
@@ -1194,6 +1265,7 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(ConvArgs p) {
     for (int i = threadIdx.x; i < (p.Cout >> 3) * 24; i += 256) p.out_split[p.out_zero_row * (p.Cout >> 3) * 24 + i] = 0;
   const int64_t total = n_live * p.Cout;
   const int64_t slab_stride = p.no_cap * p.Cout;
+  const EpiSteps on{false, p.scale != nullptr, p.shift != nullptr, p.residual != nullptr};   // the slabs hold scaled sums
   float mx = 0.0f;
   for (int64_t t = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) * 4; t < total; t += (int64_t)gridDim.x * blockDim.x * 4) {
     if ((p.Cout & 3) == 0) {
@@ -1230,11 +1302,7 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(ConvArgs p) {
       const float scv[4] = {sc4.x, sc4.y, sc4.z, sc4.w}, shv[4] = {sh4.x, sh4.y, sh4.z, sh4.w}, rsv[4] = {rs4.x, rs4.y, rs4.z, rs4.w};
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        float x = v[j];
-        if (p.scale) x = x * scv[j];
-        if (p.shift) x = x + shv[j];
-        if (p.residual) x = x + rsv[j];
-        v[j] = apply_act(x, p.act);
+        v[j] = epilogue_value(on, v[j], 1.0f, scv[j], shv[j], rsv[j], p.act);
         mx = fmaxf(mx, fabsf(v[j]));
         if (p.out_split) store_split(p.out_split, t / p.Cout, p.Cout, col + j, v[j]);
       }
@@ -1244,10 +1312,8 @@ __global__ __launch_bounds__(256) void conv_reduce_kernel(ConvArgs p) {
         float x = 0.0f;
         for (int z = 0; z < p.splits; ++z) x += p.slab[(int64_t)z * slab_stride + t + j];
         const int col = (int)((t + j) % p.Cout);
-        if (p.scale) x = x * p.scale[col];
-        if (p.shift) x = x + p.shift[col];
-        if (p.residual) x = x + p.residual[t + j];
-        x = apply_act(x, p.act);
+        x = epilogue_value(on, x, 1.0f, p.scale ? p.scale[col] : 1.0f, p.shift ? p.shift[col] : 0.0f,
+                           p.residual ? p.residual[t + j] : 0.0f, p.act);
         mx = fmaxf(mx, fabsf(x));
         p.out[t + j] = x;
       }
@@ -2074,6 +2140,9 @@ __global__ __launch_bounds__(256, APF ? 3 : ((NB == 2 && !STAMP) ? 4 : 2)) void 
     }
   }
 
+  // ---- merge, slab store and tile loop stay written out here on purpose (merge_offset_halves(), slab_tile() and epilogue_tile()
+  // say the same): this is the kernel the scene's time hangs on, and its instruction stream is kept as scheduled and measured;
+  // only the per-value chain comes from epilogue_value()
   if constexpr (KS == 2) {
     // the two offset halves meet: each wave hands the row tile it does not finish to its partner through LDS (the image is
     // dead) and finishes the other -- wave (kg, wc) writes rows 32 * kg .. + 31 of columns 32 * wc .. + 31
@@ -2133,12 +2202,7 @@ __global__ __launch_bounds__(256, APF ? 3 : ((NB == 2 && !STAMP) ? 4 : 2)) void 
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const int64_t row = row0 + q + 8 * rg;
-        float v = acc[a][rg * 4 + q];
-        v = v * out_scale;
-        v = v * sc;
-        v = v + sh;
-        if (HAS_RES) v = v + res[q];
-        v = apply_act(v, act);
+        const float v = epilogue_value({true, true, true, HAS_RES}, acc[a][rg * 4 + q], out_scale, sc, sh, HAS_RES ? res[q] : 0.0f, act);
         if (col_ok && row < n_live) {
           p.out[row * Cout + col] = v;
           mx = fmaxf(mx, fabsf(v));
@@ -2206,12 +2270,7 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_gof_kernel(ConvArgs p, GoA
   int32_t pre[4];
 #pragma unroll
   for (int i = 0; i < 4; ++i) pre[i] = tr[(tid >> 3) + 32 * i];
-  const int col = cout0 + wc * 32 + (lane & 31);
-  const bool col_ok = col < Cout;
-  const int colc = col_ok ? col : 0;
-  const bool use_scale = p.scale != nullptr && p.splits == 1, use_shift = p.shift != nullptr && p.splits == 1;
-  const float sc = use_scale ? p.scale[colc] : 1.0f;
-  const float sh = use_shift ? p.shift[colc] : 0.0f;
+  const EpiCol c = epi_col(p, cout0 + wc * 32 + (lane & 31), p.scale != nullptr && p.splits == 1, p.shift != nullptr && p.splits == 1);
   if (tid < GO_BM * 27 / 8) reinterpret_cast<uint4*>(Ls)[tid] = lv;
   if (tid < 32) Us[GO_UMAX * GOF_ROW + tid] = 0.0f;          // the zero row
   const int n_groups = __builtin_amdgcn_readfirstlane(h0.x);
@@ -2341,69 +2400,23 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_gof_kernel(ConvArgs p, GoA
     }
   }
 
-  if constexpr (KS == 2) {
-    __syncthreads();
-    float* X = reinterpret_cast<float*>(gof_smem);           // 4 x 4 KB
-    float* mine = X + (wc * 2 + kg) * 1024;
-    const float* theirs = X + (wc * 2 + (kg ^ 1)) * 1024;
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[1][i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[0][i];
-    }
-    __syncthreads();
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[0][i] += theirs[i * 64 + lane];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[1][i] += theirs[i * 64 + lane];
-    }
-  }
+  if constexpr (KS == 2) merge_offset_halves(acc[0], acc[1], reinterpret_cast<float*>(gof_smem), wc, kg, lane);   // the image is dead
 
+  // exact fp32: no operand scale to undo, no bound to publish
   if (p.splits > 1) {                                        // partial tile into this split's slab; conv_reduce_kernel follows
     float* slab = p.slab + (int64_t)zs * p.no_cap * Cout;
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
       if (KS == 2 && a != kg) continue;
-      const int64_t row0 = tile0 + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-      for (int i = 0; i < 16; ++i) {
-        const int64_t row = row0 + (i & 3) + 8 * (i >> 2);
-        if (col_ok && row < n_live) slab[row * Cout + col] = acc[a][i];
-      }
+      slab_tile<false>(acc[a], tile0 + a * 32 + 4 * (lane >> 5), c.col, c.ok, 1.0f, slab, Cout, n_live);
     }
     return;
   }
-  const int act = p.act;
+  const EpiOut o{p.out, p.residual, p.act, Cout, n_live};
 #pragma unroll
   for (int a = 0; a < TM; ++a) {
     if (KS == 2 && a != kg) continue;
-    const int64_t row0 = tile0 + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-    for (int rg = 0; rg < 4; ++rg) {
-      float res[4];
-      if (HAS_RES) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t row = row0 + q + 8 * rg;
-          const int64_t rc = row < n_live ? row : n_live - 1;
-          res[q] = p.residual[rc * Cout + colc];
-        }
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const int64_t row = row0 + q + 8 * rg;
-        float v = acc[a][rg * 4 + q];
-        v = v * sc;
-        v = v + sh;
-        if (HAS_RES) v = v + res[q];
-        v = apply_act(v, act);
-        if (col_ok && row < n_live) p.out[row * Cout + col] = v;
-      }
-    }
+    epilogue_tile<false, HAS_RES>(acc[a], tile0 + a * 32 + 4 * (lane >> 5), c, 1.0f, o);
   }
 }
 
@@ -4126,7 +4139,7 @@ __global__ __launch_bounds__(256) void pairs_reduce_kernel(ConvArgs p, const int
     float v[4] = {s.x, s.y, s.z, s.w};
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      float x = v[j];
+      float x = v[j];                                       // epilogue_value()'s chain, each operand loaded behind its own test
       if (p.scale) x = x * p.scale[col + j];
       if (p.shift) x = x + p.shift[col + j];
       if (p.residual) x = x + p.residual[o * p.Cout + col + j];

@@ -186,37 +186,16 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_go_kernel(ConvArgs p, GoAr
     }
   }
 
-  if constexpr (KS == 2) {
-    // the two offset halves meet: each wave hands the row tile it does not finish to its partner through LDS (the images
-    // are dead) and finishes the other -- wave (kg, wc) writes rows 32 * kg .. + 31 of columns 32 * wc .. + 31
-    __syncthreads();
-    float* X = reinterpret_cast<float*>(&Us[0][0]);          // 4 x 4 KB of the 20-KB plane
-    float* mine = X + (wc * 2 + kg) * 1024, *theirs = X + (wc * 2 + (kg ^ 1)) * 1024;
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[1][0][i];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[0][0][i];
-    }
-    __syncthreads();
-    if (kg == 0) {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[0][0][i] += theirs[i * 64 + lane];
-    } else {
-#pragma unroll
-      for (int i = 0; i < 16; ++i) acc[1][0][i] += theirs[i * 64 + lane];
-    }
-  }
+  // (the images are dead: 4 x 4 KB of the 20-KB plane)
+  if constexpr (KS == 2) merge_offset_halves(acc[0][0], acc[1][0], reinterpret_cast<float*>(&Us[0][0]), wc, kg, lane);
 
   // ---- epilogue (as the stage kernel).  Split over channel slices: every block leaves its partial tile in its slab; with a
   // counter array (g.counters, zero between launches) the LAST block of a tile to arrive adds the slabs up in slab order --
   // the sums conv_reduce_kernel forms, bit for bit -- and finishes the tile itself: no reduce launch behind the kernel.
   // The partial tiles cross XCDs inside one kernel: they are written and read with device-scope accesses, and a release /
   // acquire fence pair stands around the counter.
-  bool partial = p.splits > 1;
   float oscale = out_scale;
-  if (partial) {
+  if (p.splits > 1) {
     float* slab = p.slab + (int64_t)zs * p.no_cap * Cout;
     const bool here = g.counters != nullptr;
 #pragma unroll
@@ -226,14 +205,7 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_go_kernel(ConvArgs p, GoAr
       for (int a = 0; a < TM; ++a) {
         if (KS == 2 && a != kg) continue;
         const int64_t row0 = tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int64_t row = row0 + (i & 3) + 8 * (i >> 2);
-          if (col < Cout && row < n_live) {
-            const float v = acc[a][b][i] * out_scale;
-            slab[row * Cout + col] = v;
-          }
-        }
+        slab_tile<true>(acc[a][b], row0, col, col < Cout, out_scale, slab, Cout, n_live);
       }
     }
     if (!here) return;                                       // conv_reduce_kernel follows
@@ -270,53 +242,27 @@ __global__ __launch_bounds__(256, 4) void sparse_conv_go_kernel(ConvArgs p, GoAr
         }
       }
     }
-    partial = false;
-    oscale = 1.0f;
+    oscale = 1.0f;                                           // the slabs hold scaled sums
   }
-  float* dst = p.out;
-  const bool use_scale = p.scale != nullptr, use_shift = p.shift != nullptr;
-  const int act = p.act;
   const bool has_res_rt = !HAS_RES && p.residual != nullptr;  // a split launch is instantiated without the residual template
   float mx = 0.0f;
+  const EpiOut o{p.out, p.residual, p.act, Cout, n_live};
+  // ablation bit 4: no stores, behind a test on the value that keeps the arithmetic alive
+  auto keep = [=](float v) { return !((abl & 16) && v != 12345.678f); };
+  auto finish = [&](auto with_res) {
 #pragma unroll
-  for (int b = 0; b < TN; ++b) {
-    const int col = cout0 + wc * (32 * TN) + b * 32 + (lane & 31);
-    const bool col_ok = col < Cout;
-    const int colc = col_ok ? col : 0;
-    const float sc = use_scale ? p.scale[colc] : 1.0f;
-    const float sh = use_shift ? p.shift[colc] : 0.0f;
+    for (int b = 0; b < TN; ++b) {
+      const EpiCol c = epi_col(p, cout0 + wc * (32 * TN) + b * 32 + (lane & 31), p.scale != nullptr, p.shift != nullptr);
 #pragma unroll
-    for (int a = 0; a < TM; ++a) {
-      if (KS == 2 && a != kg) continue;
-      const int64_t row0 = tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        float res[4];
-        if (HAS_RES || has_res_rt) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t row = row0 + q + 8 * rg;
-            const int64_t rc = row < n_live ? row : n_live - 1;
-            res[q] = p.residual[rc * Cout + colc];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t row = row0 + q + 8 * rg;
-          float v = acc[a][b][rg * 4 + q];
-          v = v * oscale;
-          v = v * sc;
-          v = v + sh;
-          if (HAS_RES || has_res_rt) v = v + res[q];
-          v = apply_act(v, act);
-          if (col_ok && row < n_live && !((abl & 16) && v != 12345.678f)) {
-            dst[row * Cout + col] = v;
-            mx = fmaxf(mx, fabsf(v));
-          }
-        }
+      for (int a = 0; a < TM; ++a) {
+        if (KS == 2 && a != kg) continue;
+        epilogue_tile<true, decltype(with_res)::value, true>(acc[a][b], tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5), c, oscale,
+                                                             o, mx, keep);
       }
     }
-  }
+  };
+  if (has_res_rt) finish(std::true_type{});                  // the one runtime residual: one branch per block, outside the tile loops
+  else finish(std::integral_constant<bool, HAS_RES>{});
   if (p.out_amax != nullptr) {
     __syncthreads();
     block_amax_publish(p.out_amax, mx, reinterpret_cast<float*>(&Us[0][0]));

@@ -125,12 +125,7 @@ __global__ __launch_bounds__(256, 2) void sparse_conv_go3_kernel(ConvArgs p, GoA
     int s_lo = 0, s_hi = ns;
     if (p.splits > 1) { s_lo = zs * g.slices_per_split; s_hi = min(ns, s_lo + g.slices_per_split); }
     const int n_stages = (s_hi - s_lo) * n_groups;
-    const int col = cout0 + wc * 32 + (lane & 31);
-    const bool col_ok = col < Cout;
-    const int colc = col_ok ? col : 0;
-    const bool use_scale = p.scale != nullptr && p.splits == 1, use_shift = p.shift != nullptr && p.splits == 1;
-    const float sc = use_scale ? p.scale[colc] : 1.0f;
-    const float sh = use_shift ? p.shift[colc] : 0.0f;
+    const EpiCol c = epi_col(p, cout0 + wc * 32 + (lane & 31), p.scale != nullptr && p.splits == 1, p.shift != nullptr && p.splits == 1);
     const uint16_t* ls0 = Ls(buf) + (lane & 31) * 27;
     // the next item; its metadata is requested in this item's first stage and parked in the other Ls / Rs buffer behind it
     const int it2 = it + mp.bpx;
@@ -317,72 +312,20 @@ __global__ __launch_bounds__(256, 2) void sparse_conv_go3_kernel(ConvArgs p, GoA
 
     // ---- the item's tile is complete: merge (KS = 2), epilogue.  The image just used is free; the other one may already
     // hold the next item's first stage.
-    unsigned char* const scratch = reinterpret_cast<unsigned char*>(Us(img ^ 1));
-    if constexpr (KS == 2) {
-      __syncthreads();
-      float* X = reinterpret_cast<float*>(scratch);          // 4 x 4 KB
-      float* mine = X + (wc * 2 + kg) * 1024;
-      const float* theirs = X + (wc * 2 + (kg ^ 1)) * 1024;
-      if (kg == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[1][i];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mine[i * 64 + lane] = acc[0][i];
-      }
-      __syncthreads();
-      if (kg == 0) {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[0][i] += theirs[i * 64 + lane];
-      } else {
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[1][i] += theirs[i * 64 + lane];
-      }
-    }
+    if constexpr (KS == 2) merge_offset_halves(acc[0], acc[1], reinterpret_cast<float*>(Us(img ^ 1)), wc, kg, lane);
     if (p.splits > 1) {                                      // partial tile into this split's slab; conv_reduce_kernel follows
       float* slab = p.slab + (int64_t)zs * p.no_cap * Cout;
 #pragma unroll
       for (int a = 0; a < TM; ++a) {
         if (KS == 2 && a != kg) continue;
-        const int64_t row0 = tile0 + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) {
-          const int64_t row = row0 + (i & 3) + 8 * (i >> 2);
-          if (col_ok && row < n_live) slab[row * Cout + col] = acc[a][i] * out_scale;
-        }
+        slab_tile<true>(acc[a], tile0 + a * 32 + 4 * (lane >> 5), c.col, c.ok, out_scale, slab, Cout, n_live);
       }
     } else {
-      const int act = p.act;
+      const EpiOut o{p.out, p.residual, p.act, Cout, n_live};
 #pragma unroll
       for (int a = 0; a < TM; ++a) {
         if (KS == 2 && a != kg) continue;
-        const int64_t row0 = tile0 + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-        for (int rg = 0; rg < 4; ++rg) {
-          float res[4];
-          if (HAS_RES) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-              const int64_t row = row0 + q + 8 * rg;
-              const int64_t rc = row < n_live ? row : n_live - 1;
-              res[q] = p.residual[rc * Cout + colc];
-            }
-          }
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t row = row0 + q + 8 * rg;
-            float v = acc[a][rg * 4 + q];
-            v = v * out_scale;
-            v = v * sc;
-            v = v + sh;
-            if (HAS_RES) v = v + res[q];
-            v = apply_act(v, act);
-            if (col_ok && row < n_live) {
-              p.out[row * Cout + col] = v;
-              mx = fmaxf(mx, fabsf(v));
-            }
-          }
-        }
+        epilogue_tile<true, HAS_RES, true>(acc[a], tile0 + a * 32 + 4 * (lane >> 5), c, out_scale, o, mx);
       }
     }
     if (STAMP && dbg && stamp_on) { go_stamp(dbg, 15); stamp_on = false; if (threadIdx.x == 0) dbg[(size_t)blockIdx.x * 16 + 14] = (unsigned long long)n_off_dbg; }

@@ -184,48 +184,18 @@ void sparse_conv_ws_kernel(ConvArgs p, const __bf16* __restrict__ wt) {
   }
   if (!ok) return;
 
+  // (as the stage kernel: a split launch sends its sums to its slab through the same chain)
   const bool partial = p.splits > 1;
-  float* dst = partial ? p.slab + (int64_t)zs * p.no_cap * Cout : p.out;
-  const int child = p.slices > 1 ? morton_child(zs) : 0, row_step = p.slices > 1 ? p.slices : 1;   // see slice_out_row()
   const bool use_scale = !partial && p.scale != nullptr, use_shift = !partial && p.shift != nullptr;
-  const int act = partial ? 0 : p.act;
   float mx = 0.0f;
+  EpiOut o{partial ? p.slab + (int64_t)zs * p.no_cap * Cout : p.out, p.residual, partial ? 0 : p.act, Cout, n_live};
+  if (p.slices > 1) { o.row_step = p.slices; o.child = morton_child(zs); }                         // see slice_out_row()
 #pragma unroll
   for (int b = 0; b < TN; ++b) {
-    const int col = cout0 + wc * (32 * TN) + b * 32 + (lane & 31);
-    const bool col_ok = col < Cout;
-    const int colc = col_ok ? col : 0;
-    const float sc = use_scale ? p.scale[colc] : 1.0f;
-    const float sh = use_shift ? p.shift[colc] : 0.0f;
+    const EpiCol c = epi_col(p, cout0 + wc * (32 * TN) + b * 32 + (lane & 31), use_scale, use_shift);
 #pragma unroll
     for (int a = 0; a < TM; ++a) {
-      const int64_t row0 = tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5);
-#pragma unroll
-      for (int rg = 0; rg < 4; ++rg) {
-        float res[4];
-        if constexpr (HAS_RES) {
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const int64_t row = row0 + q + 8 * rg;
-            const int64_t rc = row < n_live ? row : n_live - 1;
-            res[q] = p.residual[(rc * row_step + child) * Cout + colc];
-          }
-        }
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const int64_t row = row0 + q + 8 * rg;
-          float v = acc[a][b][rg * 4 + q];
-          v = v * out_scale;
-          v = v * sc;
-          v = v + sh;
-          if constexpr (HAS_RES) v = v + res[q];
-          v = apply_act(v, act);
-          if (col_ok && row < n_live) {
-            dst[(row * row_step + child) * Cout + col] = v;
-            mx = fmaxf(mx, fabsf(v));
-          }
-        }
-      }
+      epilogue_tile<true, HAS_RES, true>(acc[a][b], tile0 + wr * (32 * TM) + a * 32 + 4 * (lane >> 5), c, out_scale, o, mx);
     }
   }
   if (!partial && p.out_amax != nullptr) {
@@ -239,10 +209,7 @@ void sparse_conv_ws_kernel(ConvArgs p, const __bf16* __restrict__ wt) {
     if (arrived == NWC - 1 && lane == 0) {
       float m = amax_s[0];
       for (int i = 1; i < NWC; ++i) m = fmaxf(m, amax_s[i]);
-      const unsigned slot = (blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) & (AMAX_SLOTS - 1);
-      unsigned* d = reinterpret_cast<unsigned*>(p.out_amax + slot * AMAX_STRIDE);
-      const unsigned bits = __float_as_uint(m);
-      if (bits > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, bits);
+      amax_publish_candidate(p.out_amax, m);
     }
   }
 }

@@ -29,23 +29,6 @@ struct Box {
   static constexpr int NHV = HX * HY * HZ;   // halo voxels; LDS = NHV * 64 bytes
 };
 
-// v >= 0; every thread of the workgroup calls it; sh: WAVES floats of LDS
-template <int WAVES>
-__device__ __forceinline__ void unet_publish_bound(float* slots, float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float m = sh[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) m = fmaxf(m, sh[w]);
-    const unsigned slot = (blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) & (AMAX_SLOTS - 1);
-    unsigned* d = reinterpret_cast<unsigned*>(slots + slot * AMAX_STRIDE);
-    const unsigned bits = __float_as_uint(m);
-    if (bits > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, bits);
-  }
-}
-
 __global__ __launch_bounds__(256) void unet_absmax_kernel(const float* __restrict__ x, int64_t n, float* __restrict__ bound) {
   float mx = 0.0f;
   const bool vec = (((uintptr_t)x) & 15) == 0;
@@ -58,7 +41,7 @@ __global__ __launch_bounds__(256) void unet_absmax_kernel(const float* __restric
     }
   }
   __shared__ float sh[4];
-  unet_publish_bound<4>(bound, mx, sh);
+  block_amax_publish<4>(bound, mx, sh);
 }
 
 // one workgroup: max|w| -> the image's head {sw, 1 / sw, 0...}
@@ -203,7 +186,7 @@ __global__ __launch_bounds__(64 * WAVES) void unet_conv3_kernel(const float* __r
         }
     }
   }
-  if (bound_y != nullptr) unet_publish_bound<WAVES>(bound_y, mx, sh_max);
+  if (bound_y != nullptr) block_amax_publish<WAVES>(bound_y, mx, sh_max);
 }
 
 bool widths_ok(int Cin, int Cout) {

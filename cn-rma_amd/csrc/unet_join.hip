@@ -32,23 +32,6 @@ static_assert(32 * CHS % (64 * WAVES) == 0 && STAGE_IT % STAGE_BATCH == 0, "the 
 static_assert(CNRMA_UNET_JOIN_BOUND_WORDS == AMAX_SLOTS * AMAX_STRIDE, "the bound convention of f16x3.h");
 static_assert(CNRMA_UNET_JOIN_BOUND_WORDS == CNRMA_UNET_BOUND_WORDS, "one bound convention for the U-Net's two libraries");
 
-// v >= 0; every thread of the workgroup calls it; sh: NW floats of LDS
-template <int NW>
-__device__ __forceinline__ void unetjoin_publish_bound(float* slots, float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    float m = sh[0];
-#pragma unroll
-    for (int w = 1; w < NW; ++w) m = fmaxf(m, sh[w]);
-    const unsigned slot = (blockIdx.x + 7u * blockIdx.y + 13u * blockIdx.z) & (AMAX_SLOTS - 1);
-    unsigned* d = reinterpret_cast<unsigned*>(slots + slot * AMAX_STRIDE);
-    const unsigned bits = __float_as_uint(m);
-    if (bits > __hip_atomic_load(d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(d, bits);
-  }
-}
-
 // rows c0 .. c0 + 31 of w [rows][K] -> sw[k * WPAD + row]: lane l of an A operand reads sw[(k + (l >> 5)) * WPAD + (l & 31)]
 __device__ __forceinline__ void unetjoin_stage_weights(const float* __restrict__ w, int K, int c0, float* sw) {
   for (int i = threadIdx.x; i < 32 * K; i += 64 * WAVES) {
@@ -225,7 +208,7 @@ __global__ __launch_bounds__(64 * WAVES, 4) void unetjoin_fuse_kernel(const floa
       }
     }
   }
-  if (bound_out != nullptr) unetjoin_publish_bound<WAVES>(bound_out, mx, sh_max);
+  if (bound_out != nullptr) block_amax_publish<WAVES>(bound_out, mx, sh_max);
 }
 
 // grid: x = tiles of 256 * 4 voxels, y = batch item.  A thread owns four consecutive voxels of one item over every channel
@@ -260,7 +243,7 @@ __global__ __launch_bounds__(256) void unetjoin_observed_kernel(const float* __r
     }
   }
   __shared__ float sh[4];
-  if (bound_x != nullptr) unetjoin_publish_bound<4>(bound_x, mx, sh);
+  if (bound_x != nullptr) block_amax_publish<4>(bound_x, mx, sh);
 }
 
 bool widths_ok(int Cc, int Cf) {

@@ -168,6 +168,38 @@ def test_warp_specialised_kernel_is_bit_identical_to_the_stage_kernel(device, ci
         S.conv_tuning()
 
 
+@pytest.mark.parametrize("cin,cout", [(32, 72), (64, 64)])
+def test_warp_specialised_kernel_under_the_generative_transpose(device, cin, cout):
+    """sparse.conv_tuning(ws=N) on the generative transpose (8 weight slices, child m of parent i in row 8 i + m): the stage
+    kernel against the fp64 oracle, and the warp-specialised form bit-identical to it, outputs and magnitude bound, with scale,
+    shift and ReLU.  65 parents: one full 64-row tile and a one-row tile; Cout 72: a partial column tile"""
+    from cnrma_amd import sparse as S
+    rng = np.random.RandomState(cin + cout)
+    c, f = rand_sparse(rng, n=65, span=5, C=cin, ts=2)
+    W = (rng.randn(8, cin, cout) / np.sqrt(cin)).astype(np.float32)
+    scale, shift = (0.5 + rng.rand(cout)).astype(np.float32), (0.3 * rng.randn(cout)).astype(np.float32)
+    kw = dict(scale=torch.from_numpy(scale).to(device), shift=torch.from_numpy(shift).to(device), act="relu", precision="f16x3")
+    Wd = torch.from_numpy(W).to(device)
+    x = to_st(c, f, 2, device)
+    oc, of = SO.conv_transpose_generative(c, f, W, 2)
+    exp = SO.relu(of * scale.astype(np.float64) + shift.astype(np.float64))
+    try:
+        for shape in ("64x64", "128x64", "64x128"):
+            S.conv_tuning(shape, 1, 1, 0, 0)
+            assert S.conv_plan(x.cs.n, cin, cout, 1, "f16x3", 8)["shape"] == shape       # no silent fall-back to another tile
+            ref = S.conv_transpose_generative(x, Wd, **kw)
+            check(ref, oc, exp, same_order=False)
+            ref_f, ref_amax = ref.F.clone(), float(ref.amax.max())
+            assert ref_amax == float(ref_f.abs().max())
+            for slots in (2, 3):
+                S.conv_tuning(shape, 1, 1, 0, slots)
+                got = S.conv_transpose_generative(x, Wd, **kw)
+                assert torch.equal(got.F, ref_f), (shape, slots)
+                assert float(got.amax.max()) == ref_amax, (shape, slots)
+    finally:
+        S.conv_tuning()
+
+
 @pytest.mark.parametrize("cin,cout,n,span", [(64, 64, 6000, 14), (128, 128, 9000, 20), (256, 512, 1500, 9), (64, 128, 20000, 14)])
 def test_gather_once_convolution_vs_oracle_and_stage_kernel(device, cin, cout, n, span):
     """the gather-once form of the 3x3x3 stride-1 convolution (sparse.GO_CONV: per 64-row tile the distinct input rows are
